@@ -6,10 +6,15 @@ generateMatrix(ran) init through the MU iterations under the reference's stop ru
 maxiter 10000), then labels, integer connectivity counts (RCCL SUM all-reduce when N > 1),
 consensus = counts / R and the cophenetic correlation per k.  A is resident in HBM before timing.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  value = restarts completed by all ranks / max-over-ranks wall time.
+A plain run sets up, warms up, times the steps and prints the line (its roofline object holds what the timed
+steps' own HIP events give).  --full adds everything that takes runs of its own: the CPU baseline, the side
+kernels' HBM roofline, the one-group roofline pass (G > 1), C5's serialized per-kernel pass, C1's drop-in flow.
+--dump-outputs DIR writes what the last timed step returned (consensus, cophenetic rho, labels, iterations) as
+DIR/<name>.npy, for comparing two builds output for output (the inputs are seeded: identical from run to run).
 Scaling: default "strong" -- the fixed job (R restarts of every k, BASELINE
 north_star: "k=2..10 x 200-restart consensus ... on 8 x MI355X") is split over the N GPUs; "--scaling
 weak" gives every GPU the whole per-GPU workload (the consensus is then over R x N restarts).  C4 is
@@ -49,6 +54,28 @@ def brunet_valu_ops_per_element(k: int) -> int:
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: the last timed step's outputs as outdir/<name>.npy, float64 (every integer the engines return
+    is exact in it).  At most DUMP_MAX_BYTES in all: where the arrays exceed that, one over its equal share is written
+    as a fixed, seeded sample of its elements (the same elements in every run, so two builds still compare element for
+    element)."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items() if a is not None}
+    fits = sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) // 8
+    for name, a in arrays.items():
+        if not fits and a.size > share:
+            idx = np.sort(np.random.default_rng(20261015).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step written to {outdir}: {', '.join(sorted(arrays))}")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -153,7 +180,14 @@ def main():
     ap.add_argument("--maxiter", type=int, default=10000)
     ap.add_argument("--stop-rule", default="ref_compat", choices=["fixed", "ref_compat", "argmax_stable"])
     ap.add_argument("--restarts", type=int, default=None, help="override R (restarts per k)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (each a run of its own, outside the timed "
+                         "steps): the CPU baseline, the side kernels' roofline, the one-group roofline pass, C5's "
+                         "serialized per-kernel pass, C1's drop-in flow")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step (consensus, cophenetic rho, labels, iterations) as "
+                         "DIR/<name>.npy, float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--check-every", type=int, default=4, help="MU iterations enqueued between stop polls")
     ap.add_argument("--groups", type=int, default=0,
                     help="restart groups per GPU (engines on their own streams); 0 = auto: N1_GROUPS for the whole "
@@ -262,6 +296,7 @@ def main():
         return {k: float(r[i]) for i, k in enumerate(ks)}
 
     pending = [None]
+    last_cons = [None]   # rank 0: the consensus matrices the last step returned (--dump-outputs)
 
     def step():
         # this rank's shard as G groups, counts into `counts`, RCCL SUM all-reduce when N > 1 (nmf.r:111-117)
@@ -270,7 +305,7 @@ def main():
         cons = counts.to(torch.float64) / R
         rho = {}
         if rank == 0:
-            cons_host = cons.cpu().numpy()
+            cons_host = last_cons[0] = cons.cpu().numpy()
             if args.overlap_host:   # the cophenetic step of this sweep runs beside the next sweep's GPU work
                 prev, pending[0] = pending[0], host.submit(rho_of, cons_host)
                 rho = prev.result() if prev is not None else {}
@@ -284,8 +319,9 @@ def main():
     if pending[0] is not None:
         pending[0].result()
         pending[0] = None
-    roof_pass = timing and G > 1   # per-kernel rates from a separate one-group pass (below)
-    groups.set_timing(timing and not roof_pass, args.timing_stride)
+    overlapped = timing and G > 1     # the groups' kernels overlap: no HIP events in the timed steps
+    roof_pass = overlapped and args.full   # per-kernel rates from a separate one-group pass (below)
+    groups.set_timing(timing and not overlapped, args.timing_stride)
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -335,6 +371,9 @@ def main():
     res, rho = last
     if args.dump_iters and rank == 0:
         np.save(args.dump_iters, np.stack([np.asarray(ks)[np.arange(jb, je) % nk], res.iters]))
+    if args.dump_outputs and rank == 0:   # per-job arrays: this rank's shard; the consensus: all ranks' (all-reduced)
+        dump_outputs(args.dump_outputs, {"consensus": last_cons[0], "cophenetic_rho": [rho[k] for k in ks],
+                                         "labels": res.labels, "iters": res.iters, "stopped_early": res.stopped_early})
     total_restarts = nk * R * args.steps
     value = total_restarts / elapsed
     its = np.concatenate(iters_all)
@@ -372,7 +411,7 @@ def main():
                 kr["bound"] = "hbm"
                 kr["frac"] = kr["frac_hbm"]
             kernels[names[kid]] = kr
-        if rank == 0:
+        if rank == 0 and args.full:
             kernels.update(side_kernels(A_dev, m, n, max(ks)))
         dom = max([x for x in ("wta", "ahtw", "small_mu") if x in kernels],
                   key=lambda s: kernels[s]["avg_ms"] * kernels[s]["launches"])
@@ -399,7 +438,7 @@ def main():
             attach_traffic(roof, kernels, dom, *tp)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cores = args.cpu_cores or min(16, len(os.sched_getaffinity(0)))
         try:
             cpu = cpu_baseline(m, n, ks, mean_iter_k, cores, args.cpu_iters, kind=args.cpu_kind)
@@ -449,15 +488,15 @@ def bench_c1(args, dev):
     -- 20 restarts (jobs in expand.grid order, job seed = seed + job_id - 1) on the bundled gct (its 1000 x 40
     matrix from tests/golden/golden.npz, written there from the reference's file), REF_COMPAT stop rule.
     A step = the batched sweep (one nmfc_engine_run: init, MU loops, labels, counts, consensus) -> `value`.
-    Beside it, timed once each: `dropin_flow` = the 20 restarts through the drop-in nmf_mu one call after another
-    (what nmf.r does unchanged on this library), and `cpu_baseline` = the same 20 calls of the REFERENCE's own
+    Beside it with --full (c1_flows), timed once each: `dropin_flow` = the 20 restarts through the drop-in nmf_mu one
+    call after another (what nmf.r does unchanged on this library), and `cpu_baseline` = the same 20 calls of the REFERENCE's own
     nmf_mu (oracle/_ref) on one core, as test_nmf.r's njobs = 1; both from the engine's init, whose W0/H0 equal
     the reference's generateMatrix(ran) bit for bit (tests/test_gpu_parity.py), and their iteration counts
     must agree with the sweep's."""
     import numpy as np
     import torch
 
-    from nmfconsensus_amd import _lib, libnmf
+    from nmfconsensus_amd import _lib
     from nmfconsensus_amd.nmf import Engine
 
     with np.load(os.path.join(ROOT, "tests", "golden", "golden.npz"), allow_pickle=False) as z:
@@ -488,9 +527,38 @@ def bench_c1(args, dev):
                         "k_solo8_mu one workgroup per restart at m <= 1024, n <= 40, ranks 2..8; k_small_mu blocks "
                         "otherwise): algorithmic flop of all restart-iterations (4mnk + 4(m+n)k^2 each) / the phase's "
                         "HIP-event duration; latency-bound (the longest restart sets it), SURVEY 8(d): C1/C2 fit in L2"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"consensus": res.consensus, "labels": res.labels, "iters": res.iters,
+                                         "stopped_early": res.stopped_early})
+    its = np.asarray(res.iters)
+    njobs = len(ks) * R
+    dropin = cpu = None
+    if args.full:
+        dropin, cpu = c1_flows(args, eng, A, ks, R, seed, its)
+    eng.close()
+    out = {
+        "metric": metric_name("C1", m, n, ks), "value": value, "unit": "restarts/s", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+        "data": "the reference's bundled 20+20x1000.gct matrix (tests/golden/golden.npz); per-job generateMatrix(ran) init",
+        "config": {"workload": "C1: test_nmf.r -- runNMFinJobs(gct 1000x40, k=2:5, num.clusterings=5, maxniter=10000, "
+                               "seed=123), 20 restarts, stop rule " + args.stop_rule,
+                   "m": m, "n": n, "ks": ks, "restarts_per_k": R, "jobs": njobs,
+                   "mean_iterations": float(its.mean()), "max_iterations": int(its.max())},
+        "dropin_flow": dropin, "roofline": roof, "cpu_baseline": cpu,
+    }
+    print(json.dumps(out), flush=True)
+
+
+def c1_flows(args, eng, A, ks, R, seed, its):
+    """bench_c1's --full part: the drop-in flow and the reference on one core, each timed once from the engine's
+    init.  Closes the engine once the init is read back, before the drop-in calls.  Returns (dropin_flow, cpu_baseline)."""
+    import numpy as np
+
+    from nmfconsensus_amd import libnmf
+
     init = eng.run(ks, R, maxiter=0, seed=seed, want_factors=True, want_counts=False)
     eng.close()
-    its = np.asarray(res.iters)
     jobs = [(np.asfortranarray(init.W[j]), np.asfortranarray(init.H[j])) for j in range(len(ks) * R)]
     devnull = os.open(os.devnull, os.O_WRONLY)
     saved = os.dup(1)
@@ -501,7 +569,6 @@ def bench_c1(args, dev):
         t0 = time.perf_counter()
         dropin_its = [libnmf.nmf_mu(A, W0, H0, args.maxiter)["maxiter"] for W0, H0 in jobs]
         t_dropin = time.perf_counter() - t0
-        cpu = None
         if not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             from pyoracle import RefLib
@@ -513,27 +580,17 @@ def bench_c1(args, dev):
         os.dup2(saved, 1)
         os.close(saved)
         os.close(devnull)
+    cpu = None
     if not args.no_cpu_baseline:
         cpu = {"value": len(jobs) / t_ref, "unit": "restarts/s", "cores": 1, "kind": "reference",
                "sample": ("the whole C1 job: the reference's own nmf_mu (oracle/_ref, scipy OpenBLAS, 1 thread) on the "
                           f"20 restarts one after another, as test_nmf.r's njobs = 1; {t_ref * 1e3:.1f} ms"),
                "iterations_equal": bool(np.array_equal(np.asarray(ref_its), its)), "host": host_cpu()}
-    out = {
-        "metric": metric_name("C1", m, n, ks), "value": value, "unit": "restarts/s", "n_gpus": 1,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "the reference's bundled 20+20x1000.gct matrix (tests/golden/golden.npz); per-job generateMatrix(ran) init",
-        "config": {"workload": "C1: test_nmf.r -- runNMFinJobs(gct 1000x40, k=2:5, num.clusterings=5, maxniter=10000, "
-                               "seed=123), 20 restarts, stop rule " + args.stop_rule,
-                   "m": m, "n": n, "ks": ks, "restarts_per_k": R, "jobs": len(jobs),
-                   "mean_iterations": float(its.mean()), "max_iterations": int(its.max())},
-        "dropin_flow": {"value": len(jobs) / t_dropin, "unit": "restarts/s",
-                        "what": "the 20 restarts through the drop-in nmf_mu one call after another (nmf.r's .C path "
-                                f"unchanged; per call k_solo_mu at k = 2..4, k_team_mu at k = 5); {t_dropin * 1e3:.1f} ms",
-                        "iterations_equal": bool(np.array_equal(np.asarray(dropin_its), its))},
-        "roofline": roof, "cpu_baseline": cpu,
-    }
-    print(json.dumps(out), flush=True)
+    dropin = {"value": len(jobs) / t_dropin, "unit": "restarts/s",
+              "what": "the 20 restarts through the drop-in nmf_mu one call after another (nmf.r's .C path "
+                      f"unchanged; per call k_solo_mu at k = 2..4, k_team_mu at k = 5); {t_dropin * 1e3:.1f} ms",
+              "iterations_equal": bool(np.array_equal(np.asarray(dropin_its), its))}
+    return dropin, cpu
 
 
 def bench_simulated_world(args, dev):
@@ -596,6 +653,8 @@ def bench_simulated_world(args, dev):
         np.save(args.dump_iters, np.stack([np.asarray(ks)[np.arange(nk * R) % nk], iters]))
     import hashlib
     counts_host = total.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"counts": counts_host, "iters": iters})   # the replay returns counts, no consensus
     counts_sha = hashlib.sha256(counts_host.tobytes()).hexdigest()
     diag_ok = bool(all(np.all(np.diagonal(counts_host[i]) == R) for i in range(nk)))
     sym_ok = bool(np.array_equal(counts_host, np.transpose(counts_host, (0, 2, 1))))
@@ -816,6 +875,7 @@ def bench_brunet(args, rank, world, local, dev):
     counts = torch.zeros((nk, n, n), dtype=torch.int32, device=dev)
     rb, re = shard_range(R, rank, world)
     timing = not args.no_timing
+    last_cons = [None]   # rank 0: the consensus matrices the last step returned (--dump-outputs)
 
     def step():
         _, res = run_sharded_brunet(eng, ks, R, rank=rank, world=world, counts_tensor=counts, maxiter=maxiter,
@@ -823,7 +883,7 @@ def bench_brunet(args, rank, world, local, dev):
         cons = counts.to(torch.float64) / R
         rho = {}
         if rank == 0:
-            C = cons.cpu().numpy()
+            C = last_cons[0] = cons.cpu().numpy()
             for i, k in enumerate(ks):
                 rho[k] = cophenetic(C[i])[0]
         return res, rho
@@ -858,8 +918,11 @@ def bench_brunet(args, rank, world, local, dev):
     # whole-sweep algorithmic rate: every restart-iteration does 8 m n k flop of rank-k products
     ks_job = np.repeat(np.array(ks), B)
     sweep_flop = float(np.sum(8.0 * m * n * ks_job * res.iters)) * world
+    if args.dump_outputs and rank == 0:   # per-job arrays: this rank's shard; the consensus: all ranks' (all-reduced)
+        dump_outputs(args.dump_outputs, {"consensus": last_cons[0], "cophenetic_rho": [rho[k] for k in ks],
+                                         "labels": res.labels, "iters": res.iters, "stopped_early": res.stopped_early})
     roof = None
-    if timing and rank == 0:
+    if args.full and timing and rank == 0:
         # Kernel roofline: the timed sweep runs several k batches concurrently on separate streams, so
         # per-launch events there overlap.  The kernels' own rates come from a serialized pass (one
         # lane) over the same matrix: every k, R restarts, 40 fixed iterations, HIP events per launch.
@@ -910,7 +973,7 @@ def bench_brunet(args, rank, world, local, dev):
                         "the fraction is a lower bound on VALU issue use; kernel rates from a serialized 40-iteration "
                         "pass per k (R restarts); rank_k_tflops counts the 8 m n k product flops alone"}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cores = args.cpu_cores or min(16, len(os.sched_getaffinity(0)))
         try:
             cpu = cpu_baseline(m, n, ks, mean_iter_k, cores, max(2, args.cpu_iters // 20), brunet=True)

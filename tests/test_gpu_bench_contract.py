@@ -39,10 +39,26 @@ def test_bench_c1_line():
     _check(d, 2, 1)
 
 
+def test_bench_c1_plain_line_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) runs nothing beside its steps: no CPU baseline, no drop-in flow.  --dump-outputs writes
+    the last step's outputs as float64 .npy, consistent with the line (--steps really sets the timed steps)."""
+    import numpy as np
+    d = _line(["--config", "C1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    _check(d, 3, 1)
+    assert d["cpu_baseline"] is None and d["dropin_flow"] is None
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert {"consensus", "labels", "iters", "stopped_early"} <= set(got)
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["consensus"].shape == (4, 40, 40) and got["labels"].shape == (20, 40)
+    assert np.array_equal(np.diagonal(got["consensus"], axis1=1, axis2=2), np.ones((4, 40)))
+    assert got["iters"].shape == (20,) and got["iters"].mean() == d["config"]["mean_iterations"]
+
+
 def test_bench_c3_line_has_the_headline_metric_and_cpu_baseline():
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         metric = json.load(f)["metric"]
-    d = _line(["--steps", "1", "--warmup", "0", "--cpu-iters", "2"], timeout=600)
+    d = _line(["--full", "--steps", "1", "--warmup", "0", "--cpu-iters", "2"], timeout=600)
     _check(d, 1, 0)
     assert d["metric"] == metric
     assert d["roofline"]["bound"] == "mfma" and d["roofline"]["unit"] == "TFLOP/s"

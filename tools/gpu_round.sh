@@ -29,7 +29,7 @@ for p in $PARTS; do
       grep -h '^{' "$OUT/profile/trace.log" | tail -1 > "$OUT/bench_under_rocprof.json"
       python3 tools/profile_agreement.py "$OUT/bench_under_rocprof.json" "$OUT/kernel_stats.csv" > "$OUT/agreement.txt" && cat "$OUT/agreement.txt" || exit 1 ;;
     c3)
-      timeout -k 10 600 python -u bench.py > "$OUT/c3_bench.json" 2> "$OUT/c3_bench.err" && line "$OUT/c3_bench.json" C3 || { tail -5 "$OUT/c3_bench.err"; exit 1; } ;;
+      timeout -k 10 600 python -u bench.py --full > "$OUT/c3_bench.json" 2> "$OUT/c3_bench.err" && line "$OUT/c3_bench.json" C3 || { tail -5 "$OUT/c3_bench.err"; exit 1; } ;;
     fixed)
       timeout -k 10 300 python -u bench.py --stop-rule fixed --maxiter 1000 --steps 1 --warmup 0 --no-cpu-baseline \
         > "$OUT/c3_fixed1000.json" 2> "$OUT/c3_fixed1000.err" && line "$OUT/c3_fixed1000.json" FIXED-1000 || { tail -5 "$OUT/c3_fixed1000.err"; exit 1; } ;;
@@ -39,14 +39,14 @@ for p in $PARTS; do
         || { tail -5 "$OUT/sim8.err"; exit 1; } ;;
     small)
       for C in C1 C2; do
-        timeout -k 10 300 python -u bench.py --config $C --steps 10 --warmup 2 > "$OUT/${C,,}_bench.json" 2> "$OUT/${C,,}_bench.err" \
+        timeout -k 10 300 python -u bench.py --full --config $C --steps 10 --warmup 2 > "$OUT/${C,,}_bench.json" 2> "$OUT/${C,,}_bench.err" \
           && line "$OUT/${C,,}_bench.json" $C || { tail -5 "$OUT/${C,,}_bench.err"; exit 1; }
       done ;;
     c4)
-      timeout -k 10 600 python -u bench.py --config C4 --steps 1 --warmup 1 --cpu-iters 4 > "$OUT/c4_bench.json" 2> "$OUT/c4_bench.err" \
+      timeout -k 10 600 python -u bench.py --full --config C4 --steps 1 --warmup 1 --cpu-iters 4 > "$OUT/c4_bench.json" 2> "$OUT/c4_bench.err" \
         && line "$OUT/c4_bench.json" C4 || { tail -5 "$OUT/c4_bench.err"; exit 1; } ;;
     c5)
-      timeout -k 10 600 python -u bench.py --config C5 --steps 1 --warmup 1 > "$OUT/c5_bench.json" 2> "$OUT/c5_bench.err" \
+      timeout -k 10 600 python -u bench.py --full --config C5 --steps 1 --warmup 1 > "$OUT/c5_bench.json" 2> "$OUT/c5_bench.err" \
         && line "$OUT/c5_bench.json" C5 || { tail -5 "$OUT/c5_bench.err"; exit 1; } ;;
     latency)
       timeout -k 10 300 python -u tools/nmf_mu_latency.py 3 > "$OUT/nmf_mu_latency.json" 2> "$OUT/nmf_mu_latency.err" && echo "latency ok" || exit 1 ;;
