@@ -3,7 +3,12 @@
 
 Bars as for the MU path: init bit-exact; W/H within 1e-9 relative Frobenius after a fixed count;
 stop iterations, labels, connectivity counts and consensus bit-exact; results independent of the
-restart shard and of the group a restart is batched in.
+restart shard.
+
+No test of this file runs more than NMFC_BR_SMALL_B (32) restarts of one k, so every run here takes
+br_dispatch's small-batch form: one restart per workgroup on both sides, no batched reciprocal.  The
+tuned groups of several restarts per workgroup, and independence of the group a restart is batched in,
+are tested in tests/test_gpu_brunet_groups.py.
 """
 import numpy as np
 import pytest
@@ -89,6 +94,9 @@ def test_consensus_sweep_matches_oracle(gct_brunet, oracle, golden):
 
 
 def test_shard_and_group_invariance(gct_brunet):
+    """9 restarts against their shards [0, 4) and [4, 9).  Both arms are small batches (at most NMFC_BR_SMALL_B
+    restarts of one k): one restart per workgroup everywhere, so this sees a dependence on the shard (seeds, slots,
+    the live list) but none on the grouping; test_gpu_brunet_groups.py compares a grouped batch with its shards."""
     ks, R = [3, 7], 9
     full = gct_brunet.run(ks, R, maxiter=60, seed=11, stopconv=2, stopfreq=10, want_factors=True)
     a = gct_brunet.run(ks, R, maxiter=60, seed=11, stopconv=2, stopfreq=10, restart_end=4, want_factors=True)
