@@ -35,8 +35,7 @@
 #include "nmfc_tuning.hpp"
 #include "rmt.hpp"
 #include "../../include/nmfc.h"
-
-void nmfc_set_error(const char* msg);
+#include "nmfc_internal.hpp"
 
 namespace {
 

@@ -16,6 +16,7 @@
 
 #include "../../include/libnmf_compat.h"
 #include "../../include/nmfc.h"
+#include "nmfc_internal.hpp"
 #include "nmfc_kernels.hpp"
 
 namespace {
@@ -139,8 +140,6 @@ void mu_cache_drop() {   // g_mu_lock held
   g_mu.a = nullptr;
 }
 }  // namespace
-
-void nmfc_solo_release();   // solo.hip
 
 void nmfc_nmf_mu_release(void) {
   {

@@ -23,15 +23,10 @@
 #include <vector>
 
 #include "../../include/nmfc.h"
+#include "nmfc_internal.hpp"
 #include "nmfc_kernels.hpp"
 
 using namespace nmfc;
-
-// solo.hip: the batched one-workgroup-per-restart kernel for rank <= 4 on gct-sized shapes
-int nmfc_solo_batch_rank(int n, int k);
-int nmfc_solo_batch_launch(const double* Acm, long a_ld, int m, int n, double* W, long w_ld, double* H, long h_ld,
-                           const nmfc::SoloJob* djobs, int njobs, int kp, int maxiter, int stop_rule, int* stop_iter,
-                           int* stop_reason, int max_wgs, hipStream_t st);
 
 namespace {
 
@@ -276,8 +271,8 @@ std::vector<SoloJob> place_solo(Packing& pk, std::vector<RestartInfo> solo, int 
 
 }  // namespace
 
-// error slot shared with the other translation units of the library (brunet.hip)
-__attribute__((visibility("hidden"))) void nmfc_set_error(const char* msg) { g_err = msg; }
+// error slot shared with the other translation units of the library (nmfc_internal.hpp)
+void nmfc_set_error(const char* msg) { g_err = msg; }
 
 struct nmfc_engine {
   int dev = 0;
@@ -375,6 +370,16 @@ bool sk_grid_fits(const nmfc_engine* e, long ngroups, int ntj) {
   const long S = ipc * (e->nsplit - 1) * nst_full + ipc * nst_last;
   return nitems >= e->ncu && S >= (long)e->ncu * nst_max;
 }
+// The one stream-K decision, for the cost model (choose_tiles) and the launch alike: the group count of the
+// stream-K launch of W^T A tile `tile` (0 big: 4-panel groups of big_panels; 3 mid: 2-panel groups of mid_panels),
+// or 0 where that tile runs one item per workgroup.  The model counts the big tile's groups from the live panels,
+// the launch from the packed ones (a multiple of WTA_NPT); pack() fills panels from 0, so the two counts agree.
+int sk_groups(const nmfc_engine* e, int tile, int big_panels, int mid_panels, int ntj) {
+  const bool big = tile == 0 && sk_big_ok(e, ntj), mid = tile == 3 && sk_mid_ok(e, ntj);
+  if (!big && !mid) return 0;
+  const int ng = big ? (big_panels + WTA_NPT - 1) / WTA_NPT : (mid_panels + 1) / 2;
+  return sk_grid_fits(e, ng, ntj) ? ng : 0;
+}
 
 TileChoice choose_tiles(const nmfc_engine* e, int np_live, int ntj) {
   const long ns = e->nsplit, cu = e->ncu;
@@ -397,8 +402,7 @@ TileChoice choose_tiles(const nmfc_engine* e, int np_live, int ntj) {
   for (const Cand& c : cands) {
     // the big and 2-panel tiles in their stream-K form (k_wta2_sk, from one whole round of items on) take wgs / slots
     // rounds, not ceil(wgs / slots): the last round's items are split over every CU
-    const bool sk = (c.id == 0 && sk_big_ok(e, ntj) && sk_grid_fits(e, (np + 3) / 4, ntj)) ||
-                    (c.id == 3 && sk_mid_ok(e, ntj) && sk_grid_fits(e, (np + 1) / 2, ntj));
+    const bool sk = sk_groups(e, c.id, (int)np, (int)np, ntj) > 0;
     const double est = sk ? c.wgs / (double)c.slots * c.t * WTA_SK_COST : std::ceil(c.wgs / (double)c.slots) * c.t;
     if (est < best - 1e-9) {
       best = est;
@@ -583,6 +587,877 @@ struct TimedLaunch {
   }
 };
 
+// ---- nmfc_engine_run: the state of one call and its phases, in the order they run (DESIGN.md "The sweep driver") ----
+
+struct PollEvents {   // destroyed on every exit path, including HCHECK returns
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~PollEvents() {
+    for (hipEvent_t x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
+struct Sweep {
+  nmfc_engine* e = nullptr;
+  nmfc_sweep_opts opts;             // resolved: defaults filled in
+  const int* ks = nullptr;
+  int nk = 0, R = 0;
+  long jb = 0;                      // the shard: jobs [jb, jb + nj) of the nk x R grid
+  int nj = 0;
+  std::vector<RestartInfo> all;     // by restart id: shard jobs in k-descending order (packing order)
+  std::vector<int> rslot;           // rid -> shard job slot
+  std::vector<int> hoff;            // rid -> first archive row
+  long sw_total = 0;                // sum of k^2: every restart's Gram block
+  bool small = false;               // the small-shape kernels run the whole sweep
+  Packing pk;                       // where the live restarts sit in the stacked W / H
+  std::vector<SmallBlock> sblocks;  // small shapes: the k_small_mu blocks
+  std::vector<SoloJob> solo;        // small shapes: the restarts the solo kernels take
+  long cap_cols = 0;                // columns of the stacked buffers (from the first packing)
+  int ntj = 0;                      // 128-sample tiles of W^T A
+  long g_ld = 0, g_split = 0, cls_ld = 0;
+  bool want_w = false, tolx = false;
+  int cur = 0;                      // which of W[2] / H[2] holds the factors
+  int nact = 0;                     // restarts in pk
+  std::vector<char> archived;       // by rid: rows already in Hfin / Wfin
+  std::vector<int> si, sr;          // by rid: host copies of stop_iter / stop_reason
+  int it = 0;                       // MU iterations enqueued
+  int polls = 0, checked = 0;       // n_stopped polls enqueued / consumed
+  int stopped_at_pack = 0;          // stopped restarts the current packing already accounts for
+  PollEvents pe;
+  long long tot_iters = 0;          // accounting: restart-iterations run, and the longest restart
+  int max_it = 0;
+  int job_k(int s) const { return ks[(jb + s) % nk]; }
+};
+
+// W / H offsets of the shard's jobs in the caller's job-major factor arrays: W_j (m x k), H_j (k x n)
+void factor_offsets(const Sweep& s, std::vector<long>& woff, std::vector<long>& ho) {
+  woff.assign(s.nj + 1, 0);
+  ho.assign(s.nj + 1, 0);
+  for (int j = 0; j < s.nj; ++j) {
+    woff[j + 1] = woff[j] + (long)s.e->m * s.job_k(j);
+    ho[j + 1] = ho[j] + (long)s.job_k(j) * s.e->n;
+  }
+}
+
+// dst (cols x rows) = src (rows x cols) transposed, both row-major: a job's H between the caller's k x n
+// column-major form (n rows of k) and the engine's k rows of n
+void transpose(const double* src, int rows, int cols, double* dst) {
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + r] = src[(size_t)r * cols + c];
+}
+
+int check_args(Sweep& s, nmfc_engine* e, const int* ks, int nk, int R, const nmfc_sweep_opts* opts_in) {
+  if (!e || !ks || nk <= 0 || R <= 0) {
+    set_err("nmfc_engine_run: bad arguments");
+    return -1;
+  }
+  s.e = e;
+  s.ks = ks;
+  s.nk = nk;
+  s.R = R;
+  nmfc_sweep_opts& opts = s.opts;
+  if (opts_in)
+    opts = *opts_in;
+  else
+    nmfc_default_opts(&opts);
+  if (opts.check_every <= 0) opts.check_every = 4;
+  const int m = e->m, n = e->n;
+  for (int i = 0; i < nk; ++i) {
+    // nmf.r:107-108 rejects k = 1; the per-restart LDS blocks hold k <= KMAX.
+    if (ks[i] < 2 || ks[i] > KMAX || ks[i] > n || ks[i] > m) {
+      set_err("nmfc_engine_run: k=%d unsupported (need 2 <= k <= min(%d, m, n))", ks[i], KMAX);
+      return -1;
+    }
+    // k_init walks a restart's m k + k n draws with 32-bit draw indices (one chunk of up to 31 x 32 past the end)
+    if ((long)m * ks[i] + (long)ks[i] * n + 31L * 32 >= (long)INT_MAX) {
+      set_err("nmfc_engine_run: m k + k n = %ld draws per restart exceeds the init kernel's 32-bit index range",
+              (long)m * ks[i] + (long)ks[i] * n);
+      return -1;
+    }
+  }
+  if (opts.maxiter < 0) {
+    set_err("nmfc_engine_run: maxiter must be >= 0");
+    return -1;
+  }
+  if (opts.stop_rule < 0 || opts.stop_rule > 3 || opts.label_rule < 0 || opts.label_rule > 1 ||
+      opts.init_stream < 0 || opts.init_stream > 1) {
+    set_err("nmfc_engine_run: bad stop rule, label rule or init stream");
+    return -1;
+  }
+  HCHECK(hipSetDevice(e->dev));
+  return 0;
+}
+
+// The shard's job range, restart ids, the small / solo split and the first packing; no device work.
+int plan_jobs(Sweep& s) {
+  nmfc_engine* e = s.e;
+  const int m = e->m, n = e->n;
+  const long njobs_all = (long)s.nk * s.R;
+  const long jb = std::max(0, s.opts.job_begin);
+  const long je = (s.opts.job_end < 0) ? njobs_all : std::min<long>(s.opts.job_end, njobs_all);
+  if (jb >= je) {
+    set_err("nmfc_engine_run: empty job range [%ld, %ld)", jb, je);
+    return -1;
+  }
+  s.jb = jb;
+  const int nj = s.nj = (int)(je - jb);
+
+  // ---- restart ids: shard jobs in k-descending order (packing order) ----
+  std::vector<int> order(nj);
+  for (int i = 0; i < nj; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return s.job_k(a) > s.job_k(b); });
+  s.all.resize(nj);
+  s.rslot.resize(nj);
+  s.hoff.assign(nj + 1, 0);
+  for (int rid = 0; rid < nj; ++rid) {
+    RestartInfo& r = s.all[rid];
+    r.k = s.job_k(order[rid]);
+    r.rid = rid;
+    r.sq_off = (int)s.sw_total;
+    r.col0 = 0;
+    s.rslot[rid] = order[rid];
+    s.sw_total += (long)r.k * r.k;
+    s.hoff[rid + 1] = s.hoff[rid] + r.k;
+  }
+  // small shapes: one persistent workgroup per 16-column block runs the whole loop (a function of m, n and
+  // the stop rule only, so a job takes the same path -- and gives the same bits -- in any batch)
+  s.small = e->small_ok && e->m_pad <= 1024 && n <= 64 && s.opts.stop_rule != NMFC_STOP_TOLX;
+  // ... and there, a restart the solo kernels take (rank 2..8 on gct-sized shapes, nmfc_mu_solo_fits: k_solo_mu for
+  // ranks 2..4, k_solo8_mu for 5..8) runs on one workgroup of its own, the others in k_small_mu blocks; the choice is a
+  // function of (m, n, k) only, so a job gives the same bits in any batch and on any number of GPUs.  Through the
+  // single-restart nmf_mu drop-in the bits are the same for ranks 2..4 only (the drop-in runs k_solo_mu there); it
+  // runs ranks 5..8 on k_team_mu (faster for one restart), whose sums run in another order
+  std::vector<RestartInfo> blk_jobs, solo_jobs;
+  for (const RestartInfo& r : s.all)
+    (s.small && e->solo_ok && nmfc_mu_solo_fits(m, n, r.k) ? solo_jobs : blk_jobs).push_back(r);
+  s.pk = s.small ? pack_small(blk_jobs, s.sblocks) : pack(s.all);
+  if (s.small && !solo_jobs.empty()) s.solo = place_solo(s.pk, solo_jobs, (int)s.sblocks.size() * 16, n);
+  s.cap_cols = (long)s.pk.npanels * PANEL;
+  s.ntj = (int)(e->n_cols_pad / 128);
+  s.g_ld = e->n_cols_pad;
+  s.g_split = s.cap_cols * s.g_ld;
+  s.cls_ld = std::max<long>(n, KMAX);
+  s.tolx = s.opts.stop_rule == NMFC_STOP_TOLX;
+  s.nact = nj;
+  s.archived.assign(nj, 0);
+  s.si.assign(nj, 0);
+  s.sr.assign(nj, 0);
+  return 0;
+}
+
+int upload_packing(nmfc_engine* e, const Packing& p) {
+  hipStream_t st = e->st;
+  HCHECK(hipMemcpyAsync(e->rinfo.p, p.ri.data(), sizeof(RestartInfo) * std::max<size_t>(p.ri.size(), 1),
+                        hipMemcpyHostToDevice, st));
+  HCHECK(hipMemcpyAsync(e->prb.p, p.prb.data(), sizeof(int) * p.npanels, hipMemcpyHostToDevice, st));
+  HCHECK(hipMemcpyAsync(e->pre.p, p.pre.data(), sizeof(int) * p.npanels, hipMemcpyHostToDevice, st));
+  HCHECK(hipMemcpyAsync(e->colinfo.p, p.ci.data(), sizeof(ColInfo) * p.ci.size(), hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+// The per-run buffers, grown to the first packing (later packings never exceed it), the packing uploaded, the stop
+// state and both factor buffers zeroed.
+int ensure_buffers(Sweep& s) {
+  nmfc_engine* e = s.e;
+  const int n = e->n, nj = s.nj;
+  const long cap_cols = s.cap_cols, fin_rows = s.hoff[nj];
+  const Packing& pk = s.pk;
+  if (e->W[0].ensure(sizeof(double) * cap_cols * e->m_pad) || e->H[0].ensure(sizeof(double) * cap_cols * e->n_pad) ||
+      e->W[1].ensure(sizeof(double) * cap_cols * e->m_pad) || e->H[1].ensure(sizeof(double) * cap_cols * e->n_pad) ||
+      e->Gpart.ensure(sizeof(double) * s.g_split * e->nsplit) || e->SWpart.ensure(sizeof(double) * s.sw_total * e->nsplit) ||
+      e->SH.ensure(sizeof(double) * s.sw_total) || e->Hfin.ensure(sizeof(double) * fin_rows * e->n_pad) ||
+      e->SHP.ensure(sizeof(double) * cap_cols * KMAX) || e->colact.ensure(sizeof(int) * cap_cols) ||
+      (s.want_w && e->Wfin.ensure(sizeof(double) * fin_rows * e->m_pad)) || e->rinfo.ensure(sizeof(RestartInfo) * nj) ||
+      e->finfo.ensure(sizeof(RestartInfo) * nj) || e->stop_iter.ensure(sizeof(int) * nj) ||
+      e->stop_reason.ensure(sizeof(int) * nj) || e->unchanged.ensure(sizeof(int) * nj) ||
+      e->classes.ensure(sizeof(int) * nj * s.cls_ld) || e->n_stopped.ensure(sizeof(int)) ||
+      e->prb.ensure(sizeof(int) * pk.npanels) || e->pre.ensure(sizeof(int) * pk.npanels) ||
+      e->colinfo.ensure(sizeof(ColInfo) * pk.npanels * PANEL) ||
+      e->moves.ensure(sizeof(MoveJob) * nj) || e->labels.ensure(sizeof(int32_t) * (size_t)nj * n) ||
+      e->slot.ensure(sizeof(int) * nj) || e->Hstat.ensure(sizeof(double) * nj))
+    return -1;
+  if (s.tolx && e->Wsnap.ensure(sizeof(double) * cap_cols * e->m_pad)) return -1;
+  hipStream_t st = e->st;
+  if (upload_packing(e, pk)) return -1;
+  HCHECK(hipMemcpyAsync(e->slot.p, s.rslot.data(), sizeof(int) * nj, hipMemcpyHostToDevice, st));
+  HCHECK(hipMemsetAsync(e->stop_iter.p, 0, sizeof(int) * nj, st));
+  HCHECK(hipMemsetAsync(e->stop_reason.p, 0, sizeof(int) * nj, st));
+  HCHECK(hipMemsetAsync(e->unchanged.p, 0, sizeof(int) * nj, st));
+  HCHECK(hipMemsetAsync(e->classes.p, 0, sizeof(int) * nj * s.cls_ld, st));   // nmf_mu.c:132 zero start
+  HCHECK(hipMemsetAsync(e->n_stopped.p, 0, sizeof(int), st));
+  HCHECK(hipMemsetAsync(e->colact.p, 0, sizeof(int) * cap_cols, st));
+  HCHECK(hipMemsetAsync(e->W[0].p, 0, sizeof(double) * cap_cols * e->m_pad, st));
+  HCHECK(hipMemsetAsync(e->H[0].p, 0, sizeof(double) * cap_cols * e->n_pad, st));
+  HCHECK(hipMemsetAsync(e->W[1].p, 0, sizeof(double) * cap_cols * e->m_pad, st));
+  HCHECK(hipMemsetAsync(e->H[1].p, 0, sizeof(double) * cap_cols * e->n_pad, st));
+  return 0;
+}
+
+// Init arm 1: caller-provided factors, shard-job-major: W_j (m x k), H_j (k x n)
+int init_from_caller(Sweep& s, const double* W_init, const double* H_init) {
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  const int m = e->m, n = e->n;
+  std::vector<long> woff, ho;
+  factor_offsets(s, woff, ho);
+  std::vector<double> hrow;
+  for (const RestartInfo& r : s.pk.ri) {
+    const int j = s.rslot[r.rid], k = r.k;
+    HCHECK(hipMemcpy2DAsync(e->W[0].as<double>() + (long)r.col0 * e->m_pad, sizeof(double) * e->m_pad,
+                            W_init + woff[j], sizeof(double) * m, sizeof(double) * m, k, hipMemcpyHostToDevice, st));
+    hrow.assign((size_t)k * n, 0.0);
+    transpose(H_init + ho[j], n, k, hrow.data());
+    HCHECK(hipMemcpy2DAsync(e->H[0].as<double>() + (long)r.col0 * e->n_pad, sizeof(double) * e->n_pad, hrow.data(),
+                            sizeof(double) * n, sizeof(double) * n, k, hipMemcpyHostToDevice, st));
+    HCHECK(hipStreamSynchronize(st));   // hrow is reused
+  }
+  return 0;
+}
+
+// Init arm 2: R's runif, nmf.r:37-38 under the BatchJobs job seed (seed + job_id - 1)
+int init_r_runif(Sweep& s) {
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  const int nj = s.nj;
+  std::vector<InitJob> ij(nj);
+  for (int i = 0; i < nj; ++i) {
+    const RestartInfo& r = s.pk.ri[i];
+    ij[i] = InitJob{(uint32_t)(s.opts.seed + (uint32_t)(s.jb + s.rslot[r.rid])), r.col0, r.k, 0};
+  }
+  if (e->initjobs.ensure(sizeof(InitJob) * nj)) return -1;
+  HCHECK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
+  {
+    TimedLaunch tl(e, KID_INIT);
+    hipLaunchKernelGGL(k_init_runif, dim3(nj), dim3(NT), 0, st, e->initjobs.as<InitJob>(), e->m, e->n, e->m_pad,
+                       e->n_pad, e->W[0].as<double>(), e->H[0].as<double>());
+  }
+  HCHECK(hipGetLastError());
+  HCHECK(hipStreamSynchronize(st));   // ij goes out of scope
+  return 0;
+}
+
+// Init arm 3: the reference's glibc rand() stream, drawn in chunks that each start from a jump of the recurrence
+int init_glibc(Sweep& s) {
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  const int m = e->m, n = e->n, nj = s.nj;
+  const Packing& pk = s.pk;
+  std::vector<InitJob> ij(nj);
+  std::vector<int> cj, ci;
+  int maxch = 1;
+  // draws per thread: halve the chunk (down to 62) while the sweep would run fewer than 65 536 threads -- the
+  // draws of one chunk are a dependent sequence, and the jump product a thread starts with costs ~1 000 ops
+  long draws = 0;
+  for (int i = 0; i < nj; ++i) draws += (long)m * pk.ri[i].k + (long)pk.ri[i].k * n;
+  int rchunk = RCHUNK;
+  while (rchunk > 62 && draws / rchunk < 65536) rchunk /= 2;
+  for (int i = 0; i < nj; ++i) {
+    const RestartInfo& r = pk.ri[i];
+    const long total = (long)m * r.k + (long)r.k * n;
+    const int nch = (int)((total + rchunk - 1) / rchunk);
+    ij[i].seed = (uint32_t)(s.opts.seed + (uint32_t)(s.jb + s.rslot[r.rid]));   // job seed = seed + job_id - 1
+    ij[i].col0 = r.col0;
+    ij[i].k = r.k;
+    ij[i].nchunks = nch;
+    maxch = std::max(maxch, nch);
+    for (int c = 0; c < nch; ++c) {
+      cj.push_back(i);
+      ci.push_back(c);
+    }
+  }
+  if (maxch > e->jump_chunks || rchunk != e->jump_rchunk) {
+    std::vector<uint32_t> tab = make_jump_table(maxch, rchunk);
+    if (e->jump.ensure(sizeof(uint32_t) * tab.size())) return -1;
+    HCHECK(hipMemcpyAsync(e->jump.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, st));
+    HCHECK(hipStreamSynchronize(st));
+    e->jump_chunks = maxch;
+    e->jump_rchunk = rchunk;
+  }
+  if (e->initjobs.ensure(sizeof(InitJob) * nj) || e->chunk_job.ensure(sizeof(int) * cj.size()) ||
+      e->chunk_idx.ensure(sizeof(int) * ci.size()))
+    return -1;
+  HCHECK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
+  HCHECK(hipMemcpyAsync(e->chunk_job.p, cj.data(), sizeof(int) * cj.size(), hipMemcpyHostToDevice, st));
+  HCHECK(hipMemcpyAsync(e->chunk_idx.p, ci.data(), sizeof(int) * ci.size(), hipMemcpyHostToDevice, st));
+  const int total_chunks = (int)cj.size();
+  {
+    TimedLaunch tl(e, KID_INIT);
+    hipLaunchKernelGGL(k_init, dim3((total_chunks + NT - 1) / NT), dim3(NT), 0, st, e->initjobs.as<InitJob>(),
+                       e->chunk_job.as<int>(), e->chunk_idx.as<int>(), total_chunks, e->jump.as<uint32_t>(), rchunk / 31,
+                       m, n, e->m_pad, e->n_pad, s.opts.min_init, s.opts.max_init, e->W[0].as<double>(),
+                       e->H[0].as<double>());
+  }
+  HCHECK(hipGetLastError());
+  HCHECK(hipStreamSynchronize(st));   // host vectors cj/ci go out of scope
+  return 0;
+}
+
+// archive rows of restarts (final H, and W when requested) from the current buffers
+int archive(Sweep& s, const std::vector<RestartInfo>& list) {
+  if (list.empty()) return 0;
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  std::vector<MoveJob> mv(list.size());
+  for (size_t x = 0; x < list.size(); ++x) mv[x] = {list[x].col0, s.hoff[list[x].rid], list[x].k};
+  HCHECK(hipMemcpyAsync(e->moves.p, mv.data(), sizeof(MoveJob) * mv.size(), hipMemcpyHostToDevice, st));
+  {
+    TimedLaunch tl(e, KID_OTHER);
+    hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 2), dim3(NT), 0, st, e->moves.as<MoveJob>(),
+                       e->H[s.cur].as<double>(), e->n_pad, e->Hfin.as<double>(), e->n_pad, e->n_pad);
+    if (s.want_w)
+      hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 16), dim3(NT), 0, st, e->moves.as<MoveJob>(),
+                         e->W[s.cur].as<double>(), e->m_pad, e->Wfin.as<double>(), e->m_pad, e->m_pad);
+  }
+  HCHECK(hipGetLastError());
+  HCHECK(hipStreamSynchronize(st));   // mv is a host temporary
+  for (const RestartInfo& r : list) s.archived[r.rid] = 1;
+  return 0;
+}
+
+// the restarts still in the packing when the sweep ends
+int archive_rest(Sweep& s) {
+  std::vector<RestartInfo> rest;
+  for (const RestartInfo& r : s.pk.ri)
+    if (!s.archived[r.rid]) rest.push_back(r);
+  return archive(s, rest);
+}
+
+// Small shapes, solo jobs beside the block kernel: on streams of their own that wait for fork_ev, one launch per
+// kernel rank, taking at most the CUs the block kernel leaves free (one workgroup of either kernel fills a CU), shared
+// in proportion to jobs x cost per iteration (tools/solo_iter_time.py: rank 2 ~3.7 us, 3..4 ~5.1, 5..8 ~10.1), each
+// workgroup running its share of jobs one after another: the block kernel's workgroups never wait for a CU behind solo
+// workgroups (the budget assumes this engine is the only one on the device; restart groups -- several engines on one
+// GPU -- are a large-shape tool and would oversubscribe it here; a speed matter only, the bits do not depend on it)
+int launch_solo_beside_blocks(Sweep& s) {
+  nmfc_engine* e = s.e;
+  const int n = e->n;
+  const std::vector<SoloJob>& solo = s.solo;
+  const long free_cu = std::max<long>(1, e->ncu - (long)s.sblocks.size());
+  auto wt = [](int kp) -> long { return kp <= 2 ? 4 : kp <= 4 ? 6 : 12; };
+  long wsum = 0;
+  for (const SoloJob& job : solo) wsum += wt(nmfc_solo_batch_rank(n, job.k));
+  std::vector<std::pair<size_t, size_t>> groups;   // [g0, g1) of one kernel rank, highest rank first
+  for (size_t g0 = 0; g0 < solo.size();) {
+    const int kp = nmfc_solo_batch_rank(n, solo[g0].k);
+    size_t g1 = g0;
+    while (g1 < solo.size() && nmfc_solo_batch_rank(n, solo[g1].k) == kp) ++g1;
+    groups.emplace_back(g0, g1);
+    g0 = g1;
+  }
+  for (int g = 0; g < (int)groups.size(); ++g) {
+    const size_t g0 = groups[g].first, g1 = groups[g].second;
+    const int kp = nmfc_solo_batch_rank(n, solo[g0].k);
+    const long nq = (long)(g1 - g0);
+    const long share = std::min<long>(nq, std::max<long>(1, free_cu * nq * wt(kp) / wsum));
+    HCHECK(hipStreamWaitEvent(e->aux[g], e->fork_ev, 0));
+    if (nmfc_solo_batch_launch(e->Acm.as<double>(), e->m_pad, e->m, n, e->W[0].as<double>(), e->m_pad,
+                               e->H[0].as<double>(), e->n_pad, e->solojobs.as<SoloJob>() + g0, (int)nq, kp,
+                               s.opts.maxiter, s.opts.stop_rule, e->stop_iter.as<int>(), e->stop_reason.as<int>(),
+                               (int)share, e->aux[g]))
+      return -1;
+    HCHECK(hipEventRecord(e->join_ev[g], e->aux[g]));
+  }
+  // the main stream joins after every launch is enqueued
+  for (int g = 0; g < (int)groups.size(); ++g) HCHECK(hipStreamWaitEvent(e->st, e->join_ev[g], 0));
+  return 0;
+}
+
+// The small-shape phase: the whole MU loop of every restart in persistent kernels (k_small_mu blocks and the solo
+// launches), one KID_SMALL scope; every restart records its own stop iteration.
+int small_phase(Sweep& s) {
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  const std::vector<SmallBlock>& sblocks = s.sblocks;
+  const std::vector<SoloJob>& solo = s.solo;
+  if (!sblocks.empty()) {
+    if (e->smallblk.ensure(sizeof(SmallBlock) * sblocks.size())) return -1;
+    HCHECK(hipMemcpyAsync(e->smallblk.p, sblocks.data(), sizeof(SmallBlock) * sblocks.size(), hipMemcpyHostToDevice, st));
+  }
+  if (!solo.empty()) {
+    if (e->solojobs.ensure(sizeof(SoloJob) * solo.size())) return -1;
+    HCHECK(hipMemcpyAsync(e->solojobs.p, solo.data(), sizeof(SoloJob) * solo.size(), hipMemcpyHostToDevice, st));
+    for (int x = 0; x < 4; ++x) {
+      if (!e->aux[x]) HCHECK(hipStreamCreateWithFlags(&e->aux[x], hipStreamNonBlocking));
+      if (!e->join_ev[x]) HCHECK(hipEventCreateWithFlags(&e->join_ev[x], hipEventDisableTiming));
+    }
+    if (!e->fork_ev) HCHECK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
+  }
+  {
+    TimedLaunch tl(e, KID_SMALL);   // the whole small-shape phase: k_small_mu blocks and the solo launches
+    const bool team = use_team(e, (int)sblocks.size());
+    // the fork point is recorded BEFORE the block kernel: an event recorded after it would hold the solo launches
+    // until the block kernel had finished (round 4: C1 24.7 ms = 9.9 + 14.8 ms serialised)
+    if (!solo.empty() && !team) HCHECK(hipEventRecord(e->fork_ev, st));
+    if (!sblocks.empty() && launch_small(e, (int)sblocks.size(), s.opts.maxiter, s.opts.stop_rule)) return -1;
+    // the solo jobs: after k_small_mu when teams run (a team's workgroups must all be resident at once: nothing else
+    // may hold CUs then) or when there are no blocks, else beside it
+    if (!solo.empty() && (sblocks.empty() || team)) {
+      // the batch's solo jobs have the GPU to themselves: ONE launch of every kernel rank, one workgroup per job
+      // in list order -- the costliest ranks first -- on the main stream (per-rank launches on streams of their
+      // own were serialised by the hardware queues they shared: C2's rank-2 launch began when the rank-4 one ended)
+      if (nmfc_solo_batch_launch(e->Acm.as<double>(), e->m_pad, e->m, e->n, e->W[0].as<double>(), e->m_pad,
+                                 e->H[0].as<double>(), e->n_pad, e->solojobs.as<SoloJob>(), (int)solo.size(), 0,
+                                 s.opts.maxiter, s.opts.stop_rule, e->stop_iter.as<int>(), e->stop_reason.as<int>(),
+                                 (int)solo.size(), st))
+        return -1;
+    } else if (!solo.empty()) {
+      if (launch_solo_beside_blocks(s)) return -1;
+    }
+  }
+  HCHECK(hipStreamSynchronize(st));
+  if (!sblocks.empty() && use_team(e, (int)sblocks.size()) && team_failed(e, (int)sblocks.size())) {
+    set_err("k_team_mu: a team of workgroups could not meet (not co-resident?)");
+    return -1;
+  }
+  if (e->timing) drain_timing(e);
+  s.it = s.opts.maxiter;   // every restart records its own stop iteration
+  return 0;
+}
+
+// ---- the MFMA path: one launch site per kernel ----
+// (the launchers stand in the order that first names each kernel as the single-function driver did: narrow, stream-K,
+// k_wta2, k_hupdate, the narrow then the full-width k_ahtw4, k_wstat.  The compiler emits kernels in that order, so the
+// code object keeps its layout.)
+
+// every k_wta2 / full-width k_ahtw4 instantiation has its template's one signature
+using Wta2Kernel = decltype(&k_wta2<1, 64, 2, 2, 1, GT_NBUF, 1, true, true, true>);
+using AhtwKernel = decltype(&k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE>);
+
+// narrow (end-of-sweep) W^T A: the restarts block-packed into the first nblk 16-column blocks
+void launch_wta_narrow(const Sweep& s, int nblk) {
+  nmfc_engine* e = s.e;
+  const int ntq = (int)(e->n_cols_pad / 16);
+  // loader / consumer waves (two waves), or the one-wave form: bit-identical
+  auto kn = e->narrow_lc ? k_wta_narrow_lc<16, NARROW_NBUF, true> : k_wta_narrow<16, NARROW_NBUF, true>;
+  hipLaunchKernelGGL(kn, dim3(e->nsplit * nblk * (ntq + 1)), dim3(e->narrow_lc ? 128 : 64), 0, e->st,
+                     e->W[s.cur].as<double>(), e->Ablk.as<double>(), e->m_pad, ntq, e->nsplit, e->kchunk, nblk,
+                     e->colinfo.as<ColInfo>(), e->Gpart.as<double>(), s.g_ld, s.g_split, e->SWpart.as<double>(),
+                     s.sw_total);
+}
+
+// stream-K form of the big (4-panel) or 2-panel tile over ng groups: ncu persistent workgroups, whole rounds of items
+// then the rest split evenly (bit-identical to the one-item-per-workgroup tile: the same MFMA chains, handed over at a
+// stage boundary).  *gsplit = 1 after a LASTSUM launch.
+int launch_wta_sk(Sweep& s, bool big, int ng, int* gsplit) {
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  if (!e->skflag.p) {
+    if (e->skfix.ensure(sizeof(double) * SK_FIX * e->ncu) || e->skflag.ensure(sizeof(unsigned) * e->ncu)) return -1;
+    HCHECK(hipMemsetAsync(e->skflag.p, 0, sizeof(unsigned) * e->ncu, st));
+  }
+  const long tiles = (long)ng * s.ntj;
+  const bool lastsum = e->wta_lastsum && big;
+  if (lastsum && e->sktcnt.bytes < sizeof(unsigned) * tiles) {
+    if (e->sktcnt.ensure(sizeof(unsigned) * tiles)) return -1;   // fresh tickets: zero
+    HCHECK(hipMemsetAsync(e->sktcnt.p, 0, sizeof(unsigned) * tiles, st));
+  }
+  const SkArgs a{e->W[s.cur].as<double>(), e->Ablk.as<double>(), e->m_pad, ng, s.ntj, e->kchunk,
+                 e->prb.as<int>(), e->pre.as<int>(), e->rinfo.as<RestartInfo>(), e->colinfo.as<ColInfo>(),
+                 e->stop_iter.as<int>(), e->Gpart.as<double>(), s.g_ld, s.g_split, e->SWpart.as<double>(), s.sw_total,
+                 e->skfix.as<double>(), e->skflag.as<unsigned>(), ++e->sk_epoch, e->nsplit,
+                 e->sktcnt.as<unsigned>(), e->sk_dp_xcd};
+  if (!big) {
+    hipLaunchKernelGGL((k_wta2_sk<WTA_MID_NBUF, false, false, 2>), dim3(e->ncu), dim3(SK_THREADS / 2), 0, st, a);
+  } else if (lastsum) {
+    hipLaunchKernelGGL((k_wta2_sk<GT_NBUF, false, true>), dim3(e->ncu), dim3(SK_THREADS), 0, st, a);
+    *gsplit = 1;   // every tile's chunk partials summed into chunk slot 0
+  } else {
+    hipLaunchKernelGGL(k_wta2_sk<GT_NBUF>, dim3(e->ncu), dim3(SK_THREADS), 0, st, a);
+  }
+  return 0;
+}
+
+// One one-item-per-workgroup W^T A launch: nsplit x ngroups x (tiles + gram_wgs) workgroups of `threads`
+struct Wta2Launch {
+  Wta2Kernel kern;
+  int threads;
+  int ngroups;    // panel groups (of the tile's 4, 2 or 1 panels)
+  int tiles;      // sample tiles per group
+  int gram_wgs;   // the 1-panel shapes: Gram workgroups of their own per (chunk, group)
+};
+
+// W^T A on the GTile core: the instantiation and grid of tile shape `tile` (TileChoice::wta) for `live` panels holding
+// restarts of `npanels` packed ones.  Every shape accumulates every entry in the same canonical K order, so the choice
+// never changes a bit.
+Wta2Launch pick_wta2(const nmfc_engine* e, int tile, int ntj, int live, int npanels) {
+  // panels holding restarts: the empty panels that pad the last 4-panel W^T A group get no 1-panel W^T A workgroups
+  const int lp = std::max(1, live);
+  if (tile == 0) {
+    // ntj >= 4: 16 waves (4 per SIMD, 64 x 32 outputs each; round 5: +2 % over 8 waves at full load, every
+    // Gram chain in registers, tools/kvar.hip), else 8 waves carrying 2 / 4 Gram candidates each
+    Wta2Kernel kw = (ntj >= 4)   ? (WTA_W16 ? k_wta2<WTA_NPT, 128, 4, 4, 1, GT_NBUF, 1, true, true, false, true>
+                                            : k_wta2<WTA_NPT, 128, 4, 2, 1, GT_NBUF, 1, true, true, false, WTA_GREG>)
+                    : (ntj >= 2) ? k_wta2<WTA_NPT, 128, 4, 2, 2, GT_NBUF, 1, true>
+                                 : k_wta2<WTA_NPT, 128, 4, 2, 4, GT_NBUF, 1, true>;
+    return {kw, (ntj >= 4 && WTA_W16) ? 1024 : 512, npanels / WTA_NPT, ntj, 0};
+  }
+  if (tile == 3) {   // npanels is a multiple of WTA_NPT, so of 2
+    // ntj >= 4: wave rows = panels (2 x 4 waves, 64 x 32 outputs each) with every Gram chain in registers
+    // (the 16-wave big tile's scheme), else 4 x 2 waves carrying LDS Gram chains
+    Wta2Kernel kw = (ntj >= 4 && WTA_MID_GREG) ? k_wta2<2, 128, 2, 4, 1, WTA_MID_NBUF, WTA_MID_MINW, true, true, false, true>
+                    : (ntj >= 2)               ? k_wta2<2, 128, 4, 2, 1, WTA_MID_NBUF, WTA_MID_MINW, true>
+                                               : k_wta2<2, 128, 4, 2, 2, WTA_MID_NBUF, WTA_MID_MINW, true>;
+    return {kw, 512, (lp + 1) / 2, ntj, 0};
+  }
+  if (tile != 2)   // 1-panel tiles: the Gram blocks in 3 workgroups of their own per (chunk, panel)
+    return {k_wta2<1, 64, 2, 2, 1, GT_NBUF, 1, true, true, true>, 256, lp, 2 * ntj, 3};
+  // few live panels: 1-panel x 32-sample tiles, two 16x16 blocks per wave (short chains);
+  // at most one live workgroup per CU: an 8-stage ring (more DMA in flight per CU, 96 KiB)
+  Wta2Kernel kw = (long)e->nsplit * live * 4 * ntj <= e->ncu ? k_wta2<1, 32, 4, 1, 1, 8, 1, true, true, true>
+                                                             : k_wta2<1, 32, 4, 1, 1, GT_NBUF, 1, true, true, true>;
+  return {kw, 256, lp, 4 * ntj, 3};
+}
+
+void launch_wta2(const Sweep& s, const Wta2Launch& l) {
+  nmfc_engine* e = s.e;
+  hipLaunchKernelGGL(l.kern, dim3(e->nsplit * l.ngroups * (l.tiles + l.gram_wgs)), dim3(l.threads), 0, e->st,
+                     e->W[s.cur].as<double>(), e->Ablk.as<double>(), e->m_pad, l.ngroups, l.tiles, e->nsplit, e->kchunk,
+                     e->prb.as<int>(), e->pre.as<int>(), e->rinfo.as<RestartInfo>(), e->colinfo.as<ColInfo>(),
+                     e->stop_iter.as<int>(), e->Gpart.as<double>(), s.g_ld, s.g_split, e->SWpart.as<double>(),
+                     s.sw_total);
+}
+
+// What one chunk of check_every iterations launches, decided once per chunk
+struct ChunkPlan {
+  TileChoice tc;   // tile shapes by grid size (a speed choice only: every shape sums in the canonical K order)
+  int nblk;        // narrow (end-of-sweep) form: the restarts sit in the first nblk 16-column blocks; else 0
+  int live;        // panels holding restarts ...
+  int lp;          // ... and at least 1: the empty panels that pad the last 4-panel W^T A group get no A h^T
+                   // workgroups (each would fetch a prologue stage before finding its panel idle)
+  int ngt_ahtw, grid_ahtw;
+  AhtwKernel ka;   // the full-width A h^T tile
+};
+
+int launch_wta(Sweep& s, const ChunkPlan& cp, int* gsplit) {
+  if (cp.nblk > 0) {
+    launch_wta_narrow(s, cp.nblk);
+  } else if (const int ng = sk_groups(s.e, cp.tc.wta, s.pk.npanels, cp.lp, s.ntj)) {
+    return launch_wta_sk(s, cp.tc.wta == 0, ng, gsplit);
+  } else {
+    launch_wta2(s, pick_wta2(s.e, cp.tc.wta, s.ntj, cp.live, s.pk.npanels));
+  }
+  return 0;
+}
+
+void launch_hupdate(const Sweep& s, int iter, int gsplit) {
+  nmfc_engine* e = s.e;
+  hipLaunchKernelGGL(k_hupdate<>, dim3(s.nact), dim3(NTH), 0, e->st, iter, s.opts.maxiter, s.opts.stop_rule,
+                     e->rinfo.as<RestartInfo>(), e->n, e->n_pad, e->Gpart.as<double>(), s.g_ld, s.g_split, gsplit,
+                     e->nsplit, e->SWpart.as<double>(), s.sw_total, e->H[s.cur].as<double>(), e->SH.as<double>(),
+                     e->stop_iter.as<int>(), e->stop_reason.as<int>(), e->unchanged.as<int>(),
+                     e->classes.as<int>(), s.cls_ld, e->n_stopped.as<int>(), e->SHP.as<double>(),
+                     e->colact.as<int>(), e->Hstat.as<double>());
+}
+
+void launch_ahtw(const Sweep& s, const ChunkPlan& cp, int iter) {
+  nmfc_engine* e = s.e;
+  if (cp.nblk > 0)   // per live 16-column block: 16 rows x 32 genes, 2 waves
+    hipLaunchKernelGGL((k_ahtw4<GT / 4, GT_NBUF, 1, 16, 2>), dim3(4 * e->ngt * cp.nblk), dim3(128), 0, e->st,
+                       iter, e->H[s.cur].as<double>(), e->n_pad, e->Arm.as<double>(), e->m_pad,
+                       e->W[s.cur].as<double>(), e->SHP.as<double>(), e->colinfo.as<ColInfo>(),
+                       e->colact.as<int>(), cp.nblk, 4 * e->ngt);
+  else
+    hipLaunchKernelGGL(cp.ka, dim3(cp.grid_ahtw), dim3(256), 0, e->st, iter, e->H[s.cur].as<double>(), e->n_pad,
+                       e->Arm.as<double>(), e->m_pad, e->W[s.cur].as<double>(), e->SHP.as<double>(),
+                       e->colinfo.as<ColInfo>(), e->colact.as<int>(), cp.lp, cp.ngt_ahtw);
+}
+
+ChunkPlan plan_chunk(const Sweep& s) {
+  const nmfc_engine* e = s.e;
+  ChunkPlan cp;
+  cp.live = live_panels(s.pk);
+  cp.lp = std::max(1, cp.live);
+  cp.tc = choose_tiles(e, cp.live, s.ntj);
+  cp.nblk = e->narrow_ok ? narrow_blocks(s.pk, e->narrow_maxb) : 0;
+  cp.ngt_ahtw = e->ngt * (cp.tc.ahtw_small ? 2 : 1);
+  cp.grid_ahtw = cp.lp * cp.ngt_ahtw;
+  // the last K stage's second half is padding (samples >= n): the KHALF form skips it
+  const bool kh = AHTW_KSKIP && AHTW_NBUF == 2 && e->n_pad - e->n >= 8;
+  cp.ka = cp.tc.ahtw_small ? (kh ? k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2>
+                                 : k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE>)
+                           : (kh ? k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2>
+                                 : k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE>);
+  return cp;
+}
+
+void launch_wstat(const Sweep& s, int iter) {
+  nmfc_engine* e = s.e;
+  hipLaunchKernelGGL(k_wstat, dim3(s.nact), dim3(NT), 0, e->st, iter, e->rinfo.as<RestartInfo>(),
+                     e->W[s.cur].as<double>(), e->Wsnap.as<double>(), e->m_pad, e->m, e->colact.as<int>(),
+                     e->Hstat.as<double>(), s.opts.TolX, s.opts.TolFun, e->stop_iter.as<int>(),
+                     e->stop_reason.as<int>(), e->n_stopped.as<int>());
+}
+
+// one MU iteration: three launches, each in a timing scope of its own (sampled every timing_stride-th iteration)
+int enqueue_iteration(Sweep& s, const ChunkPlan& cp, int iter) {
+  nmfc_engine* e = s.e;
+  const bool sample = iter % e->timing_stride == 0;
+  int gsplit = e->nsplit;   // chunk partials k_hupdate sums (1 after a LASTSUM launch)
+  {
+    TimedLaunch tl(e, KID_WTA, sample);
+    if (launch_wta(s, cp, &gsplit)) return -1;
+  }
+  {
+    TimedLaunch tl(e, KID_HUPD, sample);
+    launch_hupdate(s, iter, gsplit);
+  }
+  // STOP_TOLX (even iterations > 1): snapshot W before its update, test after it
+  const bool tol_check = s.tolx && iter > 1 && iter % 2 == 0;
+  if (tol_check)
+    HCHECK(hipMemcpyAsync(e->Wsnap.p, e->W[s.cur].p, sizeof(double) * (size_t)s.pk.npanels * PANEL * e->m_pad,
+                          hipMemcpyDeviceToDevice, e->st));
+  {
+    TimedLaunch tl(e, KID_AHTW, sample);
+    launch_ahtw(s, cp, iter);
+  }
+  if (tol_check) {
+    TimedLaunch tl(e, KID_OTHER);
+    launch_wstat(s, iter);
+  }
+  return 0;
+}
+
+// the next chunk of check_every iterations, then a poll of n_stopped behind it
+int enqueue_chunk(Sweep& s) {
+  nmfc_engine* e = s.e;
+  const int chunk = std::min(s.opts.check_every, s.opts.maxiter - s.it);
+  const ChunkPlan cp = plan_chunk(s);
+  for (int c = 1; c <= chunk; ++c)
+    if (enqueue_iteration(s, cp, s.it + c)) return -1;
+  HCHECK(hipGetLastError());
+  s.it += chunk;
+  HCHECK(hipMemcpyAsync(&e->h_stopped[s.polls & 1], e->n_stopped.p, sizeof(int), hipMemcpyDeviceToHost, e->st));
+  HCHECK(hipEventRecord(s.pe.ev[s.polls & 1], e->st));
+  ++s.polls;
+  return 0;
+}
+
+// consume polls, keeping one chunk in flight while there is more to enqueue; *stopped is the newest count read
+int consume_polls(Sweep& s, int* stopped, bool* done) {
+  const int target = (s.it < s.opts.maxiter) ? s.polls - 1 : s.polls;
+  while (s.checked < target) {
+    HCHECK(hipEventSynchronize(s.pe.ev[s.checked & 1]));
+    *stopped = s.e->h_stopped[s.checked & 1];
+    if (*stopped >= s.nj) *done = true;
+    ++s.checked;
+  }
+  return 0;
+}
+
+// Archive the restarts that stopped since the last packing and move the live ones into fewer panels of the other
+// W / H buffers.
+int repack(Sweep& s, int stopped) {
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  const int nj = s.nj;
+  HCHECK(hipStreamSynchronize(st));
+  if (e->timing) drain_timing(e);
+  s.checked = s.polls;   // every poll is now complete
+  HCHECK(hipMemcpy(s.si.data(), e->stop_iter.p, sizeof(int) * nj, hipMemcpyDeviceToHost));
+  std::vector<RestartInfo> gone, live;
+  for (const RestartInfo& r : s.pk.ri) {
+    if (!s.si[r.rid])
+      live.push_back(r);
+    else if (!s.archived[r.rid])   // stopped restarts a skipped repack (below) left in pk are archived once
+      gone.push_back(r);
+  }
+  if (archive(s, gone)) return -1;
+  Packing np = pack(live);
+  if ((long)np.npanels * PANEL > s.cap_cols) {
+    // first-fit decreasing is not monotone under removal: a (rare) larger packing would overrun
+    // the buffers sized from the initial one, so keep the current placement until the next poll
+    s.stopped_at_pack = stopped;
+    return 0;
+  }
+  std::vector<int> old_col(nj, -1);
+  for (const RestartInfo& r : live) old_col[r.rid] = r.col0;
+  std::vector<MoveJob> mv(np.ri.size());
+  for (size_t x = 0; x < np.ri.size(); ++x) mv[x] = {old_col[np.ri[x].rid], np.ri[x].col0, np.ri[x].k};
+  if (!mv.empty()) {
+    HCHECK(hipMemcpyAsync(e->moves.p, mv.data(), sizeof(MoveJob) * mv.size(), hipMemcpyHostToDevice, st));
+    {
+      TimedLaunch tl(e, KID_OTHER);
+      hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 16), dim3(NT), 0, st, e->moves.as<MoveJob>(),
+                         e->W[s.cur].as<double>(), e->m_pad, e->W[s.cur ^ 1].as<double>(), e->m_pad, e->m_pad);
+      hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 2), dim3(NT), 0, st, e->moves.as<MoveJob>(),
+                         e->H[s.cur].as<double>(), e->n_pad, e->H[s.cur ^ 1].as<double>(), e->n_pad, e->n_pad);
+    }
+    HCHECK(hipGetLastError());
+  }
+  s.cur ^= 1;
+  s.pk = np;
+  if (upload_packing(e, s.pk)) return -1;
+  HCHECK(hipStreamSynchronize(st));   // mv / pk host data uploaded
+  s.nact = (int)s.pk.ri.size();
+  s.stopped_at_pack = nj - s.nact;
+  ++e->repacks;
+  return 0;
+}
+
+// The MFMA path's poll / repack loop: chunks of check_every iterations, one always in flight behind the poll read.
+int mfma_loop(Sweep& s) {
+  nmfc_engine* e = s.e;
+  HCHECK(hipEventCreateWithFlags(&s.pe.ev[0], hipEventDisableTiming));
+  HCHECK(hipEventCreateWithFlags(&s.pe.ev[1], hipEventDisableTiming));
+  for (;;) {
+    if (s.it < s.opts.maxiter && enqueue_chunk(s)) return -1;
+    int stopped = 0;
+    bool done = false;
+    if (consume_polls(s, &stopped, &done)) return -1;
+    if (e->timing) drain_timing(e);
+    if (done || (s.it >= s.opts.maxiter && s.checked == s.polls)) break;
+    // repack when a fraction 1/repack_div of the live restarts have stopped since the last packing
+    if (stopped - s.stopped_at_pack >= std::max(1, s.nact / e->repack_div)) {
+      if (repack(s, stopped)) return -1;
+      if (s.nact == 0) break;
+    }
+  }
+  return 0;
+}
+
+// Labels of every restart from the archive, the co-clustering counts and consensus per k when asked for, and the stop
+// state back on the host (si, sr).
+int labels_counts_consensus(Sweep& s, nmfc_result* out) {
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  const int n = e->n, nj = s.nj, nk = s.nk;
+  std::vector<RestartInfo> fin(nj);
+  for (int rid = 0; rid < nj; ++rid) fin[rid] = {s.hoff[rid], s.all[rid].k, rid, s.all[rid].sq_off};
+  HCHECK(hipMemcpyAsync(e->finfo.p, fin.data(), sizeof(RestartInfo) * nj, hipMemcpyHostToDevice, st));
+  {
+    TimedLaunch tl(e, KID_LABELS);
+    hipLaunchKernelGGL(k_labels, dim3((n + NT - 1) / NT, nj), dim3(NT), 0, st, e->finfo.as<RestartInfo>(),
+                       e->slot.as<int>(), e->Hfin.as<double>(), e->n_pad, n, s.opts.label_rule, e->labels.as<int32_t>());
+  }
+  HCHECK(hipGetLastError());
+  std::vector<int> gb(nk + 1, 0), gl;
+  for (int g = 0; g < nk; ++g) {
+    gb[g] = (int)gl.size();
+    for (int j = 0; j < nj; ++j)
+      if ((s.jb + j) % nk == g) gl.push_back(j);
+  }
+  gb[nk] = (int)gl.size();
+  const size_t cnt_len = (size_t)nk * n * n;
+  if (out && (out->counts || out->consensus)) {
+    if (e->grp_begin.ensure(sizeof(int) * (nk + 1)) || e->grp_list.ensure(sizeof(int) * std::max<size_t>(gl.size(), 1)))
+      return -1;
+    HCHECK(hipMemcpyAsync(e->grp_begin.p, gb.data(), sizeof(int) * (nk + 1), hipMemcpyHostToDevice, st));
+    if (!gl.empty()) HCHECK(hipMemcpyAsync(e->grp_list.p, gl.data(), sizeof(int) * gl.size(), hipMemcpyHostToDevice, st));
+    int32_t* dcounts;
+    if (out->counts && out->counts_on_device) {
+      dcounts = out->counts;
+    } else {
+      if (e->counts_tmp.ensure(sizeof(int32_t) * cnt_len)) return -1;
+      dcounts = e->counts_tmp.as<int32_t>();
+    }
+    {
+      TimedLaunch tl(e, KID_COUNTS);
+      hipLaunchKernelGGL(k_counts, dim3((n + CNT_T - 1) / CNT_T, (n + CNT_T - 1) / CNT_T, nk), dim3(NT), 0, st, e->labels.as<int32_t>(),
+                         e->grp_begin.as<int>(), e->grp_list.as<int>(), n, dcounts);
+    }
+    HCHECK(hipGetLastError());
+    if (out->consensus) {
+      if (e->cons_tmp.ensure(sizeof(double) * cnt_len)) return -1;
+      hipLaunchKernelGGL(k_divide, dim3((unsigned)((cnt_len + NT - 1) / NT)), dim3(NT), 0, st, dcounts, (double)s.R,
+                         (long)cnt_len, e->cons_tmp.as<double>());
+      HCHECK(hipGetLastError());
+      HCHECK(hipMemcpyAsync(out->consensus, e->cons_tmp.p, sizeof(double) * cnt_len, hipMemcpyDeviceToHost, st));
+    }
+    if (out->counts && !out->counts_on_device)
+      HCHECK(hipMemcpyAsync(out->counts, dcounts, sizeof(int32_t) * cnt_len, hipMemcpyDeviceToHost, st));
+  }
+  HCHECK(hipMemcpyAsync(s.si.data(), e->stop_iter.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+  HCHECK(hipMemcpyAsync(s.sr.data(), e->stop_reason.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+  if (out && out->labels)
+    HCHECK(hipMemcpyAsync(out->labels, e->labels.p, sizeof(int32_t) * (size_t)nj * n, hipMemcpyDeviceToHost, st));
+  HCHECK(hipStreamSynchronize(st));   // fin, gb, gl uploaded; si, sr and the caller's arrays filled
+  if (e->timing) drain_timing(e);
+  return 0;
+}
+
+// Per-launch flops and bytes of each kernel id (nmfc_engine_kernel_flops / _bytes: the roofline of the bench line),
+// from every restart's iteration count, and the per-job iteration counts of the result.  Host only.
+void account_kernels(Sweep& s, nmfc_result* out) {
+  nmfc_engine* e = s.e;
+  const int m = e->m, n = e->n, nj = s.nj;
+  double fl_wta = 0, fl_ahtw = 0;
+  // bytes, summed over restart-iterations (each restart takes part in `itr` launches of each MU kernel)
+  double b_wta = 0, ba_wta = 0, b_ahtw = 0, ba_ahtw = 0, b_hupd = 0, ba_hupd = 0, b_lab = 0;
+  const double ns = e->nsplit;
+  for (int rid = 0; rid < nj; ++rid) {
+    const int itr = s.si[rid] ? s.si[rid] : s.it;
+    s.tot_iters += itr;
+    s.max_it = std::max(s.max_it, itr);
+    const double k = s.all[rid].k;
+    // algorithmic flops (nmf_mu.c:174-202 at 2*M*N*K each): W^T A + W^T W  |  A h^T + W0 (h h^T)
+    fl_wta += (double)itr * (2.0 * m * n * k + 2.0 * m * k * k);
+    fl_ahtw += (double)itr * (2.0 * m * n * k + 2.0 * m * k * k);
+    // W^T A: W read + G written (algorithmic) | + the split-K partials and Gram partials (design)
+    ba_wta += itr * 8.0 * k * (m + n);
+    b_wta += itr * 8.0 * k * (m + ns * n + ns * k);
+    // A h^T + W update: h, W0 read, W written
+    ba_ahtw += itr * 8.0 * k * (2.0 * m + n);
+    b_ahtw += itr * 8.0 * k * (2.0 * m + n + KMAX);
+    // H update (SURVEY 8(d) B_ew, H side): H, numerator, denominator read, H written = 32 n k
+    ba_hupd += itr * 32.0 * n * k;
+    b_hupd += itr * 8.0 * (k * n * (ns + 2.0) + k * k * (ns + 2.0) + k * KMAX);
+    b_lab += 8.0 * k * n + 4.0 * n;
+    if (out && out->iters) out->iters[s.rslot[rid]] = itr;
+    if (out && out->stopped_early) out->stopped_early[s.rslot[rid]] = (s.sr[rid] == 1 || s.sr[rid] == 3);
+  }
+  const double a_bytes = 8.0 * m * n;   // A, read once per launch by each contraction
+  if (const long long c = e->klaunch[KID_WTA]) {
+    e->kflops[KID_WTA] = fl_wta / c;
+    e->kbytes_algo[KID_WTA] = a_bytes + ba_wta / c;
+    e->kbytes[KID_WTA] = a_bytes + b_wta / c;
+  }
+  if (const long long c = e->klaunch[KID_AHTW]) {
+    e->kflops[KID_AHTW] = fl_ahtw / c;
+    e->kbytes_algo[KID_AHTW] = a_bytes + ba_ahtw / c;
+    e->kbytes[KID_AHTW] = a_bytes + b_ahtw / c;
+  }
+  if (const long long c = e->klaunch[KID_SMALL]) {   // the whole MU iteration in one persistent launch
+    e->kflops[KID_SMALL] = (fl_wta + fl_ahtw) / c;
+    e->kbytes_algo[KID_SMALL] = (ba_wta + ba_ahtw + ba_hupd) / c;
+    e->kbytes[KID_SMALL] = e->kbytes_algo[KID_SMALL];
+  }
+  if (const long long c = e->klaunch[KID_HUPD]) {
+    e->kbytes_algo[KID_HUPD] = ba_hupd / c;
+    e->kbytes[KID_HUPD] = b_hupd / c;
+  }
+  if (e->klaunch[KID_LABELS]) e->kbytes[KID_LABELS] = e->kbytes_algo[KID_LABELS] = b_lab;   // one launch
+  if (e->klaunch[KID_COUNTS]) {   // labels of each k group read once, n x n int32 counts written per k
+    e->kbytes_algo[KID_COUNTS] = 4.0 * nj * n + 4.0 * s.nk * n * n;
+    e->kbytes[KID_COUNTS] = e->kbytes_algo[KID_COUNTS];
+  }
+}
+
+// The archived factors back to the caller, shard-job-major as init_from_caller reads them
+int download_factors(Sweep& s, nmfc_result* out) {
+  if (!out || !(out->W || out->H)) return 0;
+  nmfc_engine* e = s.e;
+  hipStream_t st = e->st;
+  const int m = e->m, n = e->n;
+  std::vector<long> woff, ho;
+  factor_offsets(s, woff, ho);
+  std::vector<double> hrow;
+  for (int rid = 0; rid < s.nj; ++rid) {
+    const int j = s.rslot[rid], k = s.all[rid].k;
+    if (out->W)
+      HCHECK(hipMemcpy2DAsync(out->W + woff[j], sizeof(double) * m, e->Wfin.as<double>() + (long)s.hoff[rid] * e->m_pad,
+                              sizeof(double) * e->m_pad, sizeof(double) * m, k, hipMemcpyDeviceToHost, st));
+    if (out->H) {
+      hrow.assign((size_t)k * n, 0.0);
+      HCHECK(hipMemcpy2DAsync(hrow.data(), sizeof(double) * n, e->Hfin.as<double>() + (long)s.hoff[rid] * e->n_pad,
+                              sizeof(double) * e->n_pad, sizeof(double) * n, k, hipMemcpyDeviceToHost, st));
+      HCHECK(hipStreamSynchronize(st));
+      transpose(hrow.data(), k, n, out->H + ho[j]);
+    }
+  }
+  HCHECK(hipStreamSynchronize(st));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -704,25 +1579,15 @@ void nmfc_engine_destroy(nmfc_engine* e) {
   if (e->st) (void)hipStreamSynchronize(e->st);
   drain_timing(e);
   for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
-  DevBuf* bufs[] = {&e->Acm,       &e->Arm,       &e->Ablk,      &e->W[0],      &e->W[1],     &e->H[0],       &e->H[1],
-                    &e->Gpart,     &e->SWpart,    &e->SH,        &e->SHP,      &e->colact,     &e->Hfin,
-                    &e->Wfin,      &e->rinfo,
-                    &e->stop_iter, &e->stop_reason, &e->unchanged, &e->classes, &e->n_stopped, &e->prb,
-                    &e->pre,       &e->colinfo,   &e->moves,     &e->finfo,     &e->initjobs, &e->chunk_job,  &e->chunk_idx,
-                    &e->jump,      &e->labels,    &e->slot,      &e->grp_begin, &e->grp_list,  &e->counts_tmp,
-                    &e->cons_tmp,  &e->Hstat,     &e->Wsnap,     &e->smallblk,  &e->teamG,    &e->teamSW,
-                    &e->teamFlag,  &e->mu1_dev,   &e->mu1_G,     &e->mu1_SW,    &e->mu1_flag};
-  for (DevBuf* b : bufs) b->release();
-  e->solojobs.release();
-  for (int q = 0; q < 4; ++q) {
-    if (e->aux[q]) (void)hipStreamDestroy(e->aux[q]);
-    if (e->join_ev[q]) (void)hipEventDestroy(e->join_ev[q]);
+  for (int x = 0; x < 4; ++x) {
+    if (e->aux[x]) (void)hipStreamDestroy(e->aux[x]);
+    if (e->join_ev[x]) (void)hipEventDestroy(e->join_ev[x]);
   }
   if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
   if (e->h_stopped) (void)hipHostFree(e->h_stopped);
   if (e->mu1_host) (void)hipHostFree(e->mu1_host);
   if (e->st) (void)hipStreamDestroy(e->st);
-  delete e;
+  delete e;   // every DevBuf member frees itself
 }
 
 int nmfc_engine_device(const nmfc_engine* e) { return e ? e->dev : -1; }
@@ -757,707 +1622,46 @@ double nmfc_engine_kernel_bytes(nmfc_engine* e, int kid, double* algo_bytes_out)
 
 int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_sweep_opts* opts_in,
                     const double* W_init, const double* H_init, nmfc_result* out) {
-  if (!e || !ks || nk <= 0 || R <= 0) {
-    set_err("nmfc_engine_run: bad arguments");
-    return -1;
-  }
-  nmfc_sweep_opts opts;
-  if (opts_in)
-    opts = *opts_in;
-  else
-    nmfc_default_opts(&opts);
-  if (opts.check_every <= 0) opts.check_every = 4;
-  const int m = e->m, n = e->n;
-  for (int q = 0; q < nk; ++q) {
-    // nmf.r:107-108 rejects k = 1; the per-restart LDS blocks hold k <= KMAX.
-    if (ks[q] < 2 || ks[q] > KMAX || ks[q] > n || ks[q] > m) {
-      set_err("nmfc_engine_run: k=%d unsupported (need 2 <= k <= min(%d, m, n))", ks[q], KMAX);
-      return -1;
-    }
-    // k_init walks a restart's m k + k n draws with 32-bit draw indices (one chunk of up to 31 x 32 past the end)
-    if ((long)m * ks[q] + (long)ks[q] * n + 31L * 32 >= (long)INT_MAX) {
-      set_err("nmfc_engine_run: m k + k n = %ld draws per restart exceeds the init kernel's 32-bit index range",
-              (long)m * ks[q] + (long)ks[q] * n);
-      return -1;
-    }
-  }
-  if (opts.maxiter < 0) {
-    set_err("nmfc_engine_run: maxiter must be >= 0");
-    return -1;
-  }
-  if (opts.stop_rule < 0 || opts.stop_rule > 3 || opts.label_rule < 0 || opts.label_rule > 1 ||
-      opts.init_stream < 0 || opts.init_stream > 1) {
-    set_err("nmfc_engine_run: bad stop rule, label rule or init stream");
-    return -1;
-  }
-  HCHECK(hipSetDevice(e->dev));
-  auto t_start = std::chrono::steady_clock::now();
-  for (int q = 0; q < KID_N; ++q) {
-    e->kms[q] = 0;
-    e->kcount[q] = 0;
-    e->klaunch[q] = 0;
-    e->kflops[q] = 0;
-    e->kbytes[q] = 0;
-    e->kbytes_algo[q] = 0;
+  using clk = std::chrono::steady_clock;
+  Sweep s;
+  if (check_args(s, e, ks, nk, R, opts_in)) return -1;
+  const auto t_start = clk::now();
+  for (int x = 0; x < KID_N; ++x) {
+    e->kms[x] = 0;
+    e->kcount[x] = 0;
+    e->klaunch[x] = 0;
+    e->kflops[x] = 0;
+    e->kbytes[x] = 0;
+    e->kbytes_algo[x] = 0;
   }
   e->repacks = 0;
-  const long njobs_all = (long)nk * R;
-  const long jb = std::max(0, opts.job_begin);
-  const long je = (opts.job_end < 0) ? njobs_all : std::min<long>(opts.job_end, njobs_all);
-  if (jb >= je) {
-    set_err("nmfc_engine_run: empty job range [%ld, %ld)", jb, je);
+  s.want_w = out && out->W;
+  if (plan_jobs(s) || ensure_buffers(s)) return -1;
+  if (W_init && H_init ? init_from_caller(s, W_init, H_init)
+                       : s.opts.init_stream == NMFC_INIT_R_RUNIF ? init_r_runif(s) : init_glibc(s))
     return -1;
-  }
-  const int nj = (int)(je - jb);
-  auto job_k = [&](int s) { return ks[(jb + s) % nk]; };
-
-  // ---- restart ids: shard jobs in k-descending order (packing order) ----
-  std::vector<int> order(nj);
-  for (int i = 0; i < nj; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return job_k(a) > job_k(b); });
-  std::vector<RestartInfo> all(nj);
-  std::vector<int> rslot(nj);          // rid -> shard job slot
-  std::vector<int> hoff(nj + 1, 0);    // rid -> first archive row
-  long sw_total = 0;
-  for (int rid = 0; rid < nj; ++rid) {
-    const int s = order[rid];
-    all[rid].k = job_k(s);
-    all[rid].rid = rid;
-    all[rid].sq_off = (int)sw_total;
-    all[rid].col0 = 0;
-    rslot[rid] = s;
-    sw_total += (long)all[rid].k * all[rid].k;
-    hoff[rid + 1] = hoff[rid] + all[rid].k;
-  }
-  // small shapes: one persistent workgroup per 16-column block runs the whole loop (a function of m, n and
-  // the stop rule only, so a job takes the same path -- and gives the same bits -- in any batch)
-  const bool small = e->small_ok && e->m_pad <= 1024 && n <= 64 && opts.stop_rule != NMFC_STOP_TOLX;
-  std::vector<SmallBlock> sblocks;
-  // ... and there, a restart the solo kernels take (rank 2..8 on gct-sized shapes, nmfc_mu_solo_fits: k_solo_mu for
-  // ranks 2..4, k_solo8_mu for 5..8) runs on one workgroup of its own, the others in k_small_mu blocks; the choice is a
-  // function of (m, n, k) only, so a job gives the same bits in any batch and on any number of GPUs.  Through the
-  // single-restart nmf_mu drop-in the bits are the same for ranks 2..4 only (the drop-in runs k_solo_mu there); it
-  // runs ranks 5..8 on k_team_mu (faster for one restart), whose sums run in another order
-  std::vector<RestartInfo> blk_jobs, solo_jobs;
-  for (const RestartInfo& r : all) (small && e->solo_ok && nmfc_mu_solo_fits(m, n, r.k) ? solo_jobs : blk_jobs).push_back(r);
-  Packing pk = small ? pack_small(blk_jobs, sblocks) : pack(all);
-  std::vector<SoloJob> solo;
-  if (small && !solo_jobs.empty()) solo = place_solo(pk, solo_jobs, (int)sblocks.size() * 16, n);
-  const long cap_cols = (long)pk.npanels * PANEL;
-  const int ntj = (int)(e->n_cols_pad / 128);
-  const long g_ld = e->n_cols_pad;
-  const long g_split = cap_cols * g_ld;
-  const long cls_ld = std::max<long>(n, KMAX);
-  const long fin_rows = hoff[nj];
-  const bool want_w = out && out->W;
-
-  // ---- device buffers ----
-  if (e->W[0].ensure(sizeof(double) * cap_cols * e->m_pad) || e->H[0].ensure(sizeof(double) * cap_cols * e->n_pad) ||
-      e->W[1].ensure(sizeof(double) * cap_cols * e->m_pad) || e->H[1].ensure(sizeof(double) * cap_cols * e->n_pad) ||
-      e->Gpart.ensure(sizeof(double) * g_split * e->nsplit) || e->SWpart.ensure(sizeof(double) * sw_total * e->nsplit) ||
-      e->SH.ensure(sizeof(double) * sw_total) || e->Hfin.ensure(sizeof(double) * fin_rows * e->n_pad) ||
-      e->SHP.ensure(sizeof(double) * cap_cols * KMAX) || e->colact.ensure(sizeof(int) * cap_cols) ||
-      (want_w && e->Wfin.ensure(sizeof(double) * fin_rows * e->m_pad)) || e->rinfo.ensure(sizeof(RestartInfo) * nj) ||
-      e->finfo.ensure(sizeof(RestartInfo) * nj) || e->stop_iter.ensure(sizeof(int) * nj) ||
-      e->stop_reason.ensure(sizeof(int) * nj) || e->unchanged.ensure(sizeof(int) * nj) ||
-      e->classes.ensure(sizeof(int) * nj * cls_ld) || e->n_stopped.ensure(sizeof(int)) ||
-      e->prb.ensure(sizeof(int) * pk.npanels) || e->pre.ensure(sizeof(int) * pk.npanels) ||
-      e->colinfo.ensure(sizeof(ColInfo) * pk.npanels * PANEL) ||
-      e->moves.ensure(sizeof(MoveJob) * nj) || e->labels.ensure(sizeof(int32_t) * (size_t)nj * n) ||
-      e->slot.ensure(sizeof(int) * nj) || e->Hstat.ensure(sizeof(double) * nj))
-    return -1;
-  const bool tolx = opts.stop_rule == NMFC_STOP_TOLX;
-  if (tolx && e->Wsnap.ensure(sizeof(double) * cap_cols * e->m_pad)) return -1;
-  hipStream_t st = e->st;
-  int cur = 0;
-  auto upload_packing = [&](const Packing& p) -> int {
-    HCHECK(hipMemcpyAsync(e->rinfo.p, p.ri.data(), sizeof(RestartInfo) * std::max<size_t>(p.ri.size(), 1),
-                          hipMemcpyHostToDevice, st));
-    HCHECK(hipMemcpyAsync(e->prb.p, p.prb.data(), sizeof(int) * p.npanels, hipMemcpyHostToDevice, st));
-    HCHECK(hipMemcpyAsync(e->pre.p, p.pre.data(), sizeof(int) * p.npanels, hipMemcpyHostToDevice, st));
-    HCHECK(hipMemcpyAsync(e->colinfo.p, p.ci.data(), sizeof(ColInfo) * p.ci.size(), hipMemcpyHostToDevice, st));
-    return 0;
-  };
-  if (upload_packing(pk)) return -1;
-  HCHECK(hipMemcpyAsync(e->slot.p, rslot.data(), sizeof(int) * nj, hipMemcpyHostToDevice, st));
-  HCHECK(hipMemsetAsync(e->stop_iter.p, 0, sizeof(int) * nj, st));
-  HCHECK(hipMemsetAsync(e->stop_reason.p, 0, sizeof(int) * nj, st));
-  HCHECK(hipMemsetAsync(e->unchanged.p, 0, sizeof(int) * nj, st));
-  HCHECK(hipMemsetAsync(e->classes.p, 0, sizeof(int) * nj * cls_ld, st));   // nmf_mu.c:132 zero start
-  HCHECK(hipMemsetAsync(e->n_stopped.p, 0, sizeof(int), st));
-  HCHECK(hipMemsetAsync(e->colact.p, 0, sizeof(int) * cap_cols, st));
-  HCHECK(hipMemsetAsync(e->W[0].p, 0, sizeof(double) * cap_cols * e->m_pad, st));
-  HCHECK(hipMemsetAsync(e->H[0].p, 0, sizeof(double) * cap_cols * e->n_pad, st));
-  HCHECK(hipMemsetAsync(e->W[1].p, 0, sizeof(double) * cap_cols * e->m_pad, st));
-  HCHECK(hipMemsetAsync(e->H[1].p, 0, sizeof(double) * cap_cols * e->n_pad, st));
-
-  // ---- init ----
-  if (W_init && H_init) {
-    // caller-provided factors, shard-job-major: W_j (m x k), H_j (k x n)
-    std::vector<long> woff(nj + 1, 0), ho(nj + 1, 0);
-    for (int s = 0; s < nj; ++s) {
-      woff[s + 1] = woff[s] + (long)m * job_k(s);
-      ho[s + 1] = ho[s] + (long)job_k(s) * n;
-    }
-    std::vector<double> hrow;
-    for (const RestartInfo& r : pk.ri) {
-      const int s = rslot[r.rid], k = r.k;
-      HCHECK(hipMemcpy2DAsync(e->W[0].as<double>() + (long)r.col0 * e->m_pad, sizeof(double) * e->m_pad,
-                              W_init + woff[s], sizeof(double) * m, sizeof(double) * m, k, hipMemcpyHostToDevice, st));
-      hrow.assign((size_t)k * n, 0.0);
-      for (int j = 0; j < n; ++j)
-        for (int a = 0; a < k; ++a) hrow[(size_t)a * n + j] = H_init[ho[s] + (long)j * k + a];
-      HCHECK(hipMemcpy2DAsync(e->H[0].as<double>() + (long)r.col0 * e->n_pad, sizeof(double) * e->n_pad, hrow.data(),
-                              sizeof(double) * n, sizeof(double) * n, k, hipMemcpyHostToDevice, st));
-      HCHECK(hipStreamSynchronize(st));   // hrow is reused
-    }
-  } else if (opts.init_stream == NMFC_INIT_R_RUNIF) {
-    // nmf.r:37-38 under the BatchJobs job seed (seed + job_id - 1)
-    std::vector<InitJob> ij(nj);
-    for (int q = 0; q < nj; ++q) {
-      const RestartInfo& r = pk.ri[q];
-      ij[q] = InitJob{(uint32_t)(opts.seed + (uint32_t)(jb + rslot[r.rid])), r.col0, r.k, 0};
-    }
-    if (e->initjobs.ensure(sizeof(InitJob) * nj)) return -1;
-    HCHECK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
-    {
-      TimedLaunch tl(e, KID_INIT);
-      hipLaunchKernelGGL(k_init_runif, dim3(nj), dim3(NT), 0, st, e->initjobs.as<InitJob>(), m, n, e->m_pad, e->n_pad,
-                         e->W[0].as<double>(), e->H[0].as<double>());
-    }
-    HCHECK(hipGetLastError());
-    HCHECK(hipStreamSynchronize(st));   // ij goes out of scope
-  } else {
-    std::vector<InitJob> ij(nj);
-    std::vector<int> cj, ci;
-    int maxch = 1;
-    // draws per thread: halve the chunk (down to 62) while the sweep would run fewer than 65 536 threads -- the
-    // draws of one chunk are a dependent sequence, and the jump product a thread starts with costs ~1 000 ops
-    long draws = 0;
-    for (int q = 0; q < nj; ++q) draws += (long)m * pk.ri[q].k + (long)pk.ri[q].k * n;
-    int rchunk = RCHUNK;
-    while (rchunk > 62 && draws / rchunk < 65536) rchunk /= 2;
-    for (int q = 0; q < nj; ++q) {
-      const RestartInfo& r = pk.ri[q];
-      const long total = (long)m * r.k + (long)r.k * n;
-      const int nch = (int)((total + rchunk - 1) / rchunk);
-      ij[q].seed = (uint32_t)(opts.seed + (uint32_t)(jb + rslot[r.rid]));   // job seed = seed + job_id - 1
-      ij[q].col0 = r.col0;
-      ij[q].k = r.k;
-      ij[q].nchunks = nch;
-      maxch = std::max(maxch, nch);
-      for (int c = 0; c < nch; ++c) {
-        cj.push_back(q);
-        ci.push_back(c);
-      }
-    }
-    if (maxch > e->jump_chunks || rchunk != e->jump_rchunk) {
-      std::vector<uint32_t> tab = make_jump_table(maxch, rchunk);
-      if (e->jump.ensure(sizeof(uint32_t) * tab.size())) return -1;
-      HCHECK(hipMemcpyAsync(e->jump.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, st));
-      HCHECK(hipStreamSynchronize(st));
-      e->jump_chunks = maxch;
-      e->jump_rchunk = rchunk;
-    }
-    if (e->initjobs.ensure(sizeof(InitJob) * nj) || e->chunk_job.ensure(sizeof(int) * cj.size()) ||
-        e->chunk_idx.ensure(sizeof(int) * ci.size()))
-      return -1;
-    HCHECK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
-    HCHECK(hipMemcpyAsync(e->chunk_job.p, cj.data(), sizeof(int) * cj.size(), hipMemcpyHostToDevice, st));
-    HCHECK(hipMemcpyAsync(e->chunk_idx.p, ci.data(), sizeof(int) * ci.size(), hipMemcpyHostToDevice, st));
-    const int total_chunks = (int)cj.size();
-    {
-      TimedLaunch tl(e, KID_INIT);
-      hipLaunchKernelGGL(k_init, dim3((total_chunks + NT - 1) / NT), dim3(NT), 0, st, e->initjobs.as<InitJob>(),
-                         e->chunk_job.as<int>(), e->chunk_idx.as<int>(), total_chunks, e->jump.as<uint32_t>(), rchunk / 31,
-                         m, n,
-                         e->m_pad, e->n_pad, opts.min_init, opts.max_init, e->W[0].as<double>(), e->H[0].as<double>());
-    }
-    HCHECK(hipGetLastError());
-    HCHECK(hipStreamSynchronize(st));   // host vectors cj/ci go out of scope
-  }
-  // archive rows of restarts (final H, and W when requested) from the current buffers
-  std::vector<char> archived(nj, 0);
-  auto archive = [&](const std::vector<RestartInfo>& list) -> int {
-    if (list.empty()) return 0;
-    std::vector<MoveJob> mv(list.size());
-    for (size_t q = 0; q < list.size(); ++q) mv[q] = {list[q].col0, hoff[list[q].rid], list[q].k};
-    HCHECK(hipMemcpyAsync(e->moves.p, mv.data(), sizeof(MoveJob) * mv.size(), hipMemcpyHostToDevice, st));
-    {
-      TimedLaunch tl(e, KID_OTHER);
-      hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 2), dim3(NT), 0, st, e->moves.as<MoveJob>(),
-                         e->H[cur].as<double>(), e->n_pad, e->Hfin.as<double>(), e->n_pad, e->n_pad);
-      if (want_w)
-        hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 16), dim3(NT), 0, st, e->moves.as<MoveJob>(),
-                           e->W[cur].as<double>(), e->m_pad, e->Wfin.as<double>(), e->m_pad, e->m_pad);
-    }
-    HCHECK(hipGetLastError());
-    HCHECK(hipStreamSynchronize(st));   // mv is a host temporary
-    for (const RestartInfo& r : list) archived[r.rid] = 1;
-    return 0;
-  };
 
   // ---- iterate ----
-  auto t_iter0 = std::chrono::steady_clock::now();
-  int it = 0, q = 0, checked = 0;
-  if (small) {
-    if (!sblocks.empty()) {
-      if (e->smallblk.ensure(sizeof(SmallBlock) * sblocks.size())) return -1;
-      HCHECK(hipMemcpyAsync(e->smallblk.p, sblocks.data(), sizeof(SmallBlock) * sblocks.size(), hipMemcpyHostToDevice, st));
-    }
-    if (!solo.empty()) {
-      if (e->solojobs.ensure(sizeof(SoloJob) * solo.size())) return -1;
-      HCHECK(hipMemcpyAsync(e->solojobs.p, solo.data(), sizeof(SoloJob) * solo.size(), hipMemcpyHostToDevice, st));
-      for (int q = 0; q < 4; ++q) {
-        if (!e->aux[q]) HCHECK(hipStreamCreateWithFlags(&e->aux[q], hipStreamNonBlocking));
-        if (!e->join_ev[q]) HCHECK(hipEventCreateWithFlags(&e->join_ev[q], hipEventDisableTiming));
-      }
-      if (!e->fork_ev) HCHECK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
-    }
-    {
-      TimedLaunch tl(e, KID_SMALL);   // the whole small-shape phase: k_small_mu blocks and the solo launches
-      const bool team = use_team(e, (int)sblocks.size());
-      // the fork point is recorded BEFORE the block kernel: an event recorded after it would hold the solo launches
-      // until the block kernel had finished (round 4: C1 24.7 ms = 9.9 + 14.8 ms serialised)
-      if (!solo.empty() && !team) HCHECK(hipEventRecord(e->fork_ev, st));
-      if (!sblocks.empty() && launch_small(e, (int)sblocks.size(), opts.maxiter, opts.stop_rule)) return -1;
-      if (!solo.empty()) {
-        // after k_small_mu when teams run (a team's workgroups must all be resident at once: nothing else may hold CUs
-        // then), else beside it on streams of their own, one launch per kernel rank, taking at most the CUs it leaves
-        // free (one workgroup of either kernel fills a CU), shared in proportion to jobs x cost per iteration
-        // (tools/solo_iter_time.py: rank 2 ~3.7 us, 3..4 ~5.1, 5..8 ~10.1), each workgroup running its share of jobs
-        // one after another: the block kernel's workgroups never wait for a CU behind solo workgroups (the budget
-        // assumes this engine is the only one on the device; restart groups -- several engines on one GPU -- are a
-        // large-shape tool and would oversubscribe it here; a speed matter only, the bits do not depend on it)
-        const bool alone = sblocks.empty() || team;
-        if (alone) {
-          // the batch's solo jobs have the GPU to themselves: ONE launch of every kernel rank, one workgroup per job
-          // in list order -- the costliest ranks first -- on the main stream (per-rank launches on streams of their
-          // own were serialised by the hardware queues they shared: C2's rank-2 launch began when the rank-4 one ended)
-          if (nmfc_solo_batch_launch(e->Acm.as<double>(), e->m_pad, m, n, e->W[0].as<double>(), e->m_pad,
-                                     e->H[0].as<double>(), e->n_pad, e->solojobs.as<SoloJob>(), (int)solo.size(), 0,
-                                     opts.maxiter, opts.stop_rule, e->stop_iter.as<int>(), e->stop_reason.as<int>(),
-                                     (int)solo.size(), st))
-            return -1;
-        } else {
-          const long free_cu = std::max<long>(1, e->ncu - (long)sblocks.size());
-          auto wt = [](int kp) -> long { return kp <= 2 ? 4 : kp <= 4 ? 6 : 12; };
-          long wsum = 0;
-          for (const SoloJob& jb : solo) wsum += wt(nmfc_solo_batch_rank(n, jb.k));
-          std::vector<std::pair<size_t, size_t>> groups;   // [g0, g1) of one kernel rank, highest rank first
-          for (size_t g0 = 0; g0 < solo.size();) {
-            const int kp = nmfc_solo_batch_rank(n, solo[g0].k);
-            size_t g1 = g0;
-            while (g1 < solo.size() && nmfc_solo_batch_rank(n, solo[g1].k) == kp) ++g1;
-            groups.emplace_back(g0, g1);
-            g0 = g1;
-          }
-          for (int q = 0; q < (int)groups.size(); ++q) {
-            const size_t g0 = groups[q].first, g1 = groups[q].second;
-            const int kp = nmfc_solo_batch_rank(n, solo[g0].k);
-            const long nq = (long)(g1 - g0);
-            const long share = std::min<long>(nq, std::max<long>(1, free_cu * nq * wt(kp) / wsum));
-            HCHECK(hipStreamWaitEvent(e->aux[q], e->fork_ev, 0));
-            if (nmfc_solo_batch_launch(e->Acm.as<double>(), e->m_pad, m, n, e->W[0].as<double>(), e->m_pad,
-                                       e->H[0].as<double>(), e->n_pad, e->solojobs.as<SoloJob>() + g0, (int)nq, kp,
-                                       opts.maxiter, opts.stop_rule, e->stop_iter.as<int>(), e->stop_reason.as<int>(),
-                                       (int)share, e->aux[q]))
-              return -1;
-            HCHECK(hipEventRecord(e->join_ev[q], e->aux[q]));
-          }
-          // the main stream joins after every launch is enqueued
-          for (int q = 0; q < (int)groups.size(); ++q) HCHECK(hipStreamWaitEvent(st, e->join_ev[q], 0));
-        }
-      }
-    }
-    HCHECK(hipStreamSynchronize(st));
-    if (!sblocks.empty() && use_team(e, (int)sblocks.size()) && team_failed(e, (int)sblocks.size())) {
-      set_err("k_team_mu: a team of workgroups could not meet (not co-resident?)");
-      return -1;
-    }
-    if (e->timing) drain_timing(e);
-    it = opts.maxiter;   // every restart records its own stop iteration
-  }
-  int nact = nj;
-  int stopped_at_pack = 0;
-  struct PollEvents {   // destroyed on every exit path, including HCHECK returns
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~PollEvents() {
-      for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } pe;
-  hipEvent_t* ev = pe.ev;
-  HCHECK(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-  HCHECK(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
-  std::vector<int> si(nj);
-  for (; !small;) {
-    if (it < opts.maxiter) {
-      const int chunk = std::min(opts.check_every, opts.maxiter - it);
-      // tile shapes by grid size (a speed choice only: every shape sums in the canonical K order)
-      const TileChoice tc = choose_tiles(e, live_panels(pk), ntj);
-      bool wta_big = tc.wta == 0, wta_mid = tc.wta == 3, wta_tiny = tc.wta == 2;
-      bool ahtw_small = tc.ahtw_small;
-      // narrow (end-of-sweep) form: the restarts block-packed into the first nblk 16-column blocks
-      const int nblk = e->narrow_ok ? narrow_blocks(pk, e->narrow_maxb) : 0;
-      const bool narrow = nblk > 0;
-      const int ngt_ahtw = e->ngt * (ahtw_small ? 2 : 1);
-      // panels holding restarts: the empty panels that pad the last 4-panel W^T A group get no A h^T
-      // workgroups (each would fetch a prologue stage before finding its panel idle) and no 1-panel W^T A ones
-      const int lp = std::max(1, live_panels(pk));
-      const int grid_ahtw = lp * ngt_ahtw;
-      for (int c = 1; c <= chunk; ++c) {
-        const int iter = it + c;
-        int gsplit = e->nsplit;
-        {
-          // W^T A on the GTile core: 4-panel x 128-sample tiles (8 waves) while the grid fills the chip
-          // at least twice, else 1-panel x 64-sample tiles (4 waves).  Both accumulate every entry in
-          // the same canonical K order, so the switch never changes a bit.
-          TimedLaunch tl(e, KID_WTA, iter % e->timing_stride == 0);
-          gsplit = e->nsplit;   // chunk partials k_hupdate sums (1 after a LASTSUM launch)
-          if (narrow) {
-            const int ntq = (int)(e->n_cols_pad / 16);
-            if (e->narrow_lc)   // loader / consumer waves (bit-identical to the one-wave form)
-              hipLaunchKernelGGL((k_wta_narrow_lc<16, NARROW_NBUF, true>), dim3(e->nsplit * nblk * (ntq + 1)), dim3(128), 0,
-                                 st, e->W[cur].as<double>(), e->Ablk.as<double>(), e->m_pad, ntq, e->nsplit, e->kchunk,
-                                 nblk, e->colinfo.as<ColInfo>(), e->Gpart.as<double>(), g_ld, g_split,
-                                 e->SWpart.as<double>(), sw_total);
-            else
-              hipLaunchKernelGGL((k_wta_narrow<16, NARROW_NBUF, true>), dim3(e->nsplit * nblk * (ntq + 1)), dim3(64), 0, st,
-                                 e->W[cur].as<double>(), e->Ablk.as<double>(), e->m_pad, ntq, e->nsplit, e->kchunk, nblk,
-                                 e->colinfo.as<ColInfo>(),
-                                 e->Gpart.as<double>(), g_ld, g_split, e->SWpart.as<double>(), sw_total);
-          } else if ((wta_big && sk_big_ok(e, ntj) && sk_grid_fits(e, pk.npanels / WTA_NPT, ntj)) ||
-                     (wta_mid && sk_mid_ok(e, ntj) && sk_grid_fits(e, (lp + 1) / 2, ntj))) {
-            // stream-K form: ncu persistent workgroups, whole rounds of items then the rest split evenly (bit-identical
-            // to the one-item-per-workgroup tile: the same MFMA chains, handed over at a stage boundary)
-            if (!e->skflag.p) {
-              if (e->skfix.ensure(sizeof(double) * SK_FIX * e->ncu) || e->skflag.ensure(sizeof(unsigned) * e->ncu)) return -1;
-              HCHECK(hipMemsetAsync(e->skflag.p, 0, sizeof(unsigned) * e->ncu, st));
-            }
-            const int ng = wta_big ? pk.npanels / WTA_NPT : (lp + 1) / 2;
-            const long tiles = (long)ng * ntj;
-            const bool lastsum = e->wta_lastsum && wta_big;
-            if (lastsum && e->sktcnt.bytes < sizeof(unsigned) * tiles) {
-              if (e->sktcnt.ensure(sizeof(unsigned) * tiles)) return -1;   // fresh tickets: zero
-              HCHECK(hipMemsetAsync(e->sktcnt.p, 0, sizeof(unsigned) * tiles, st));
-            }
-            const SkArgs a{e->W[cur].as<double>(), e->Ablk.as<double>(), e->m_pad, ng, ntj, e->kchunk,
-                           e->prb.as<int>(), e->pre.as<int>(), e->rinfo.as<RestartInfo>(), e->colinfo.as<ColInfo>(),
-                           e->stop_iter.as<int>(), e->Gpart.as<double>(), g_ld, g_split, e->SWpart.as<double>(), sw_total,
-                           e->skfix.as<double>(), e->skflag.as<unsigned>(), ++e->sk_epoch, e->nsplit,
-                           e->sktcnt.as<unsigned>(), e->sk_dp_xcd};
-            if (!wta_big) {
-              hipLaunchKernelGGL((k_wta2_sk<WTA_MID_NBUF, false, false, 2>), dim3(e->ncu), dim3(SK_THREADS / 2), 0, st, a);
-            } else if (lastsum) {
-              hipLaunchKernelGGL((k_wta2_sk<GT_NBUF, false, true>), dim3(e->ncu), dim3(SK_THREADS), 0, st, a);
-              gsplit = 1;   // every tile's chunk partials summed into chunk slot 0
-            } else {
-              hipLaunchKernelGGL(k_wta2_sk<GT_NBUF>, dim3(e->ncu), dim3(SK_THREADS), 0, st, a);
-            }
-          } else if (wta_big) {
-            const int ng = pk.npanels / WTA_NPT;
-            // ntj >= 4: 16 waves (4 per SIMD, 64 x 32 outputs each; round 5: +2 % over 8 waves at full load, every
-            // Gram chain in registers, tools/kvar.hip), else 8 waves carrying 2 / 4 Gram candidates each
-            auto kw = (ntj >= 4)   ? (WTA_W16 ? k_wta2<WTA_NPT, 128, 4, 4, 1, GT_NBUF, 1, true, true, false, true>
-                                              : k_wta2<WTA_NPT, 128, 4, 2, 1, GT_NBUF, 1, true, true, false, WTA_GREG>)
-                      : (ntj >= 2) ? k_wta2<WTA_NPT, 128, 4, 2, 2, GT_NBUF, 1, true>
-                                   : k_wta2<WTA_NPT, 128, 4, 2, 4, GT_NBUF, 1, true>;
-            const int wthr = (ntj >= 4 && WTA_W16) ? 1024 : 512;
-            hipLaunchKernelGGL(kw, dim3(e->nsplit * ng * ntj), dim3(wthr), 0, st, e->W[cur].as<double>(),
-                               e->Ablk.as<double>(), e->m_pad, ng, ntj, e->nsplit, e->kchunk, e->prb.as<int>(),
-                               e->pre.as<int>(), e->rinfo.as<RestartInfo>(), e->colinfo.as<ColInfo>(),
-                               e->stop_iter.as<int>(), e->Gpart.as<double>(), g_ld, g_split, e->SWpart.as<double>(),
-                               sw_total);
-          } else if (wta_mid) {   // npanels is a multiple of WTA_NPT, so of 2
-            const int ng = (lp + 1) / 2;
-            // ntj >= 4: wave rows = panels (2 x 4 waves, 64 x 32 outputs each) with every Gram chain in registers
-            // (the 16-wave big tile's scheme), else 4 x 2 waves carrying LDS Gram chains
-            auto kw = (ntj >= 4 && WTA_MID_GREG) ? k_wta2<2, 128, 2, 4, 1, WTA_MID_NBUF, WTA_MID_MINW, true, true, false, true>
-                      : (ntj >= 2)               ? k_wta2<2, 128, 4, 2, 1, WTA_MID_NBUF, WTA_MID_MINW, true>
-                                                 : k_wta2<2, 128, 4, 2, 2, WTA_MID_NBUF, WTA_MID_MINW, true>;
-            hipLaunchKernelGGL(kw, dim3(e->nsplit * ng * ntj), dim3(512), 0, st, e->W[cur].as<double>(),
-                               e->Ablk.as<double>(), e->m_pad, ng, ntj, e->nsplit, e->kchunk, e->prb.as<int>(),
-                               e->pre.as<int>(), e->rinfo.as<RestartInfo>(), e->colinfo.as<ColInfo>(),
-                               e->stop_iter.as<int>(), e->Gpart.as<double>(), g_ld, g_split, e->SWpart.as<double>(),
-                               sw_total);
-          } else if (!wta_tiny) {   // 1-panel tiles: the Gram blocks in 3 workgroups of their own per (chunk, panel)
-            hipLaunchKernelGGL((k_wta2<1, 64, 2, 2, 1, GT_NBUF, 1, true, true, true>), dim3(e->nsplit * lp * (2 * ntj + 3)), dim3(256),
-                               0, st, e->W[cur].as<double>(), e->Ablk.as<double>(), e->m_pad, lp, 2 * ntj, e->nsplit,
-                               e->kchunk, e->prb.as<int>(), e->pre.as<int>(), e->rinfo.as<RestartInfo>(),
-                               e->colinfo.as<ColInfo>(), e->stop_iter.as<int>(), e->Gpart.as<double>(), g_ld, g_split,
-                               e->SWpart.as<double>(), sw_total);
-          } else {   // few live panels: 1-panel x 32-sample tiles, two 16x16 blocks per wave (short chains);
-                     // at most one live workgroup per CU: an 8-stage ring (more DMA in flight per CU, 96 KiB)
-            auto kw = (long)e->nsplit * live_panels(pk) * 4 * ntj <= e->ncu ? k_wta2<1, 32, 4, 1, 1, 8, 1, true, true, true>
-                                                                             : k_wta2<1, 32, 4, 1, 1, GT_NBUF, 1, true, true, true>;
-            hipLaunchKernelGGL(kw, dim3(e->nsplit * lp * (4 * ntj + 3)), dim3(256), 0, st,
-                               e->W[cur].as<double>(), e->Ablk.as<double>(), e->m_pad, lp, 4 * ntj, e->nsplit,
-                               e->kchunk, e->prb.as<int>(), e->pre.as<int>(), e->rinfo.as<RestartInfo>(),
-                               e->colinfo.as<ColInfo>(), e->stop_iter.as<int>(), e->Gpart.as<double>(), g_ld, g_split,
-                               e->SWpart.as<double>(), sw_total);
-          }
-        }
-        {
-          TimedLaunch tl(e, KID_HUPD, iter % e->timing_stride == 0);
-          hipLaunchKernelGGL(k_hupdate<>, dim3(nact), dim3(NTH), 0, st, iter, opts.maxiter, opts.stop_rule,
-                             e->rinfo.as<RestartInfo>(), n, e->n_pad, e->Gpart.as<double>(), g_ld, g_split, gsplit, e->nsplit,
-                             e->SWpart.as<double>(), sw_total, e->H[cur].as<double>(), e->SH.as<double>(),
-                             e->stop_iter.as<int>(), e->stop_reason.as<int>(), e->unchanged.as<int>(),
-                             e->classes.as<int>(), cls_ld, e->n_stopped.as<int>(), e->SHP.as<double>(),
-                             e->colact.as<int>(), e->Hstat.as<double>());
-        }
-        // STOP_TOLX (even iterations > 1): snapshot W before its update, test after it
-        const bool tol_check = tolx && iter > 1 && iter % 2 == 0;
-        if (tol_check)
-          HCHECK(hipMemcpyAsync(e->Wsnap.p, e->W[cur].p, sizeof(double) * (size_t)pk.npanels * PANEL * e->m_pad,
-                                hipMemcpyDeviceToDevice, st));
-        {
-          TimedLaunch tl(e, KID_AHTW, iter % e->timing_stride == 0);
-          if (narrow) {   // per live 16-column block: 16 rows x 32 genes, 2 waves
-            hipLaunchKernelGGL((k_ahtw4<GT / 4, GT_NBUF, 1, 16, 2>), dim3(4 * e->ngt * nblk), dim3(128), 0, st,
-                               iter, e->H[cur].as<double>(), e->n_pad, e->Arm.as<double>(), e->m_pad,
-                               e->W[cur].as<double>(), e->SHP.as<double>(), e->colinfo.as<ColInfo>(),
-                               e->colact.as<int>(), nblk, 4 * e->ngt);
-          } else {
-            // the last K stage's second half is padding (samples >= n): the KHALF form skips it
-            const bool kh = AHTW_KSKIP && AHTW_NBUF == 2 && e->n_pad - n >= 8;
-            auto ka = ahtw_small ? (kh ? k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2>
-                                       : k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE>)
-                                 : (kh ? k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2>
-                                       : k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE>);
-            hipLaunchKernelGGL(ka, dim3(grid_ahtw), dim3(256), 0, st, iter,
-                               e->H[cur].as<double>(), e->n_pad, e->Arm.as<double>(), e->m_pad, e->W[cur].as<double>(),
-                               e->SHP.as<double>(), e->colinfo.as<ColInfo>(), e->colact.as<int>(), lp,
-                               ngt_ahtw);
-          }
-        }
-        if (tol_check) {
-          TimedLaunch tl(e, KID_OTHER);
-          hipLaunchKernelGGL(k_wstat, dim3(nact), dim3(NT), 0, st, iter, e->rinfo.as<RestartInfo>(),
-                             e->W[cur].as<double>(), e->Wsnap.as<double>(), e->m_pad, m, e->colact.as<int>(),
-                             e->Hstat.as<double>(), opts.TolX, opts.TolFun, e->stop_iter.as<int>(),
-                             e->stop_reason.as<int>(), e->n_stopped.as<int>());
-        }
-      }
-      HCHECK(hipGetLastError());
-      it += chunk;
-      HCHECK(hipMemcpyAsync(&e->h_stopped[q & 1], e->n_stopped.p, sizeof(int), hipMemcpyDeviceToHost, st));
-      HCHECK(hipEventRecord(ev[q & 1], st));
-      ++q;
-    }
-    // consume polls, keeping one chunk in flight while there is more to enqueue
-    const int target = (it < opts.maxiter) ? q - 1 : q;
-    bool done = false;
-    int stopped = 0;
-    while (checked < target) {
-      HCHECK(hipEventSynchronize(ev[checked & 1]));
-      stopped = e->h_stopped[checked & 1];
-      if (stopped >= nj) done = true;
-      ++checked;
-    }
-    if (e->timing) drain_timing(e);
-    if (done || (it >= opts.maxiter && checked == q)) break;
-    // repack when a fraction 1/repack_div of the live restarts have stopped since the last packing
-    if (stopped - stopped_at_pack >= std::max(1, nact / e->repack_div)) {
-      HCHECK(hipStreamSynchronize(st));
-      if (e->timing) drain_timing(e);
-      checked = q;   // every poll is now complete
-      HCHECK(hipMemcpy(si.data(), e->stop_iter.p, sizeof(int) * nj, hipMemcpyDeviceToHost));
-      std::vector<RestartInfo> gone, live;
-      for (const RestartInfo& r : pk.ri) {
-        if (!si[r.rid])
-          live.push_back(r);
-        else if (!archived[r.rid])   // stopped restarts a skipped repack (below) left in pk are archived once
-          gone.push_back(r);
-      }
-      if (archive(gone)) return -1;
-      Packing np = pack(live);
-      if ((long)np.npanels * PANEL > cap_cols) {
-        // first-fit decreasing is not monotone under removal: a (rare) larger packing would overrun
-        // the buffers sized from the initial one, so keep the current placement until the next poll
-        stopped_at_pack = stopped;
-        continue;
-      }
-      std::vector<int> old_col(nj, -1);
-      for (const RestartInfo& r : live) old_col[r.rid] = r.col0;
-      std::vector<MoveJob> mv(np.ri.size());
-      for (size_t x = 0; x < np.ri.size(); ++x) mv[x] = {old_col[np.ri[x].rid], np.ri[x].col0, np.ri[x].k};
-      if (!mv.empty()) {
-        HCHECK(hipMemcpyAsync(e->moves.p, mv.data(), sizeof(MoveJob) * mv.size(), hipMemcpyHostToDevice, st));
-        {
-          TimedLaunch tl(e, KID_OTHER);
-          hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 16), dim3(NT), 0, st, e->moves.as<MoveJob>(),
-                             e->W[cur].as<double>(), e->m_pad, e->W[cur ^ 1].as<double>(), e->m_pad, e->m_pad);
-          hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 2), dim3(NT), 0, st, e->moves.as<MoveJob>(),
-                             e->H[cur].as<double>(), e->n_pad, e->H[cur ^ 1].as<double>(), e->n_pad, e->n_pad);
-        }
-        HCHECK(hipGetLastError());
-      }
-      cur ^= 1;
-      pk = np;
-      if (upload_packing(pk)) return -1;
-      HCHECK(hipStreamSynchronize(st));   // mv / pk host data uploaded
-      nact = (int)pk.ri.size();
-      stopped_at_pack = nj - nact;
-      ++e->repacks;
-      if (nact == 0) break;
-    }
-  }
-  HCHECK(hipStreamSynchronize(st));
+  const auto t_iter0 = clk::now();
+  if (s.small ? small_phase(s) : mfma_loop(s)) return -1;
+  HCHECK(hipStreamSynchronize(e->st));
   if (e->timing) drain_timing(e);
-  const int iters_enqueued = it;
-  auto t_iter1 = std::chrono::steady_clock::now();
-  {
-    std::vector<RestartInfo> rest;
-    for (const RestartInfo& r : pk.ri)
-      if (!archived[r.rid]) rest.push_back(r);
-    if (archive(rest)) return -1;
-  }
+  const auto t_iter1 = clk::now();
 
-  // ---- labels, counts (from the archive) ----
-  std::vector<RestartInfo> fin(nj);
-  for (int rid = 0; rid < nj; ++rid) fin[rid] = {hoff[rid], all[rid].k, rid, all[rid].sq_off};
-  HCHECK(hipMemcpyAsync(e->finfo.p, fin.data(), sizeof(RestartInfo) * nj, hipMemcpyHostToDevice, st));
-  {
-    TimedLaunch tl(e, KID_LABELS);
-    hipLaunchKernelGGL(k_labels, dim3((n + NT - 1) / NT, nj), dim3(NT), 0, st, e->finfo.as<RestartInfo>(),
-                       e->slot.as<int>(), e->Hfin.as<double>(), e->n_pad, n, opts.label_rule, e->labels.as<int32_t>());
-  }
-  HCHECK(hipGetLastError());
-  std::vector<int> gb(nk + 1, 0), gl;
-  for (int g = 0; g < nk; ++g) {
-    gb[g] = (int)gl.size();
-    for (int s = 0; s < nj; ++s)
-      if ((jb + s) % nk == g) gl.push_back(s);
-  }
-  gb[nk] = (int)gl.size();
-  const size_t cnt_len = (size_t)nk * n * n;
-  if (out && (out->counts || out->consensus)) {
-    if (e->grp_begin.ensure(sizeof(int) * (nk + 1)) || e->grp_list.ensure(sizeof(int) * std::max<size_t>(gl.size(), 1)))
-      return -1;
-    HCHECK(hipMemcpyAsync(e->grp_begin.p, gb.data(), sizeof(int) * (nk + 1), hipMemcpyHostToDevice, st));
-    if (!gl.empty()) HCHECK(hipMemcpyAsync(e->grp_list.p, gl.data(), sizeof(int) * gl.size(), hipMemcpyHostToDevice, st));
-    int32_t* dcounts;
-    if (out->counts && out->counts_on_device) {
-      dcounts = out->counts;
-    } else {
-      if (e->counts_tmp.ensure(sizeof(int32_t) * cnt_len)) return -1;
-      dcounts = e->counts_tmp.as<int32_t>();
-    }
-    {
-      TimedLaunch tl(e, KID_COUNTS);
-      hipLaunchKernelGGL(k_counts, dim3((n + CNT_T - 1) / CNT_T, (n + CNT_T - 1) / CNT_T, nk), dim3(NT), 0, st, e->labels.as<int32_t>(),
-                         e->grp_begin.as<int>(), e->grp_list.as<int>(), n, dcounts);
-    }
-    HCHECK(hipGetLastError());
-    if (out->consensus) {
-      if (e->cons_tmp.ensure(sizeof(double) * cnt_len)) return -1;
-      hipLaunchKernelGGL(k_divide, dim3((unsigned)((cnt_len + NT - 1) / NT)), dim3(NT), 0, st, dcounts, (double)R,
-                         (long)cnt_len, e->cons_tmp.as<double>());
-      HCHECK(hipGetLastError());
-      HCHECK(hipMemcpyAsync(out->consensus, e->cons_tmp.p, sizeof(double) * cnt_len, hipMemcpyDeviceToHost, st));
-    }
-    if (out->counts && !out->counts_on_device)
-      HCHECK(hipMemcpyAsync(out->counts, dcounts, sizeof(int32_t) * cnt_len, hipMemcpyDeviceToHost, st));
-  }
-  std::vector<int> sr(nj);
-  HCHECK(hipMemcpyAsync(si.data(), e->stop_iter.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-  HCHECK(hipMemcpyAsync(sr.data(), e->stop_reason.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-  if (out && out->labels)
-    HCHECK(hipMemcpyAsync(out->labels, e->labels.p, sizeof(int32_t) * (size_t)nj * n, hipMemcpyDeviceToHost, st));
-  HCHECK(hipStreamSynchronize(st));
-  if (e->timing) drain_timing(e);
-
-  long long tot_iters = 0;
-  int max_it = 0;
-  double fl_wta = 0, fl_ahtw = 0;
-  // bytes, summed over restart-iterations (each restart takes part in `itr` launches of each MU kernel)
-  double b_wta = 0, ba_wta = 0, b_ahtw = 0, ba_ahtw = 0, b_hupd = 0, ba_hupd = 0, b_lab = 0, cols = 0;
-  const double ns = e->nsplit;
-  for (int rid = 0; rid < nj; ++rid) {
-    const int itr = si[rid] ? si[rid] : iters_enqueued;
-    tot_iters += itr;
-    max_it = std::max(max_it, itr);
-    const double k = all[rid].k;
-    // algorithmic flops (nmf_mu.c:174-202 at 2*M*N*K each): W^T A + W^T W  |  A h^T + W0 (h h^T)
-    fl_wta += (double)itr * (2.0 * m * n * k + 2.0 * m * k * k);
-    fl_ahtw += (double)itr * (2.0 * m * n * k + 2.0 * m * k * k);
-    // W^T A: W read + G written (algorithmic) | + the split-K partials and Gram partials (design)
-    ba_wta += itr * 8.0 * k * (m + n);
-    b_wta += itr * 8.0 * k * (m + ns * n + ns * k);
-    // A h^T + W update: h, W0 read, W written
-    ba_ahtw += itr * 8.0 * k * (2.0 * m + n);
-    b_ahtw += itr * 8.0 * k * (2.0 * m + n + KMAX);
-    // H update (SURVEY 8(d) B_ew, H side): H, numerator, denominator read, H written = 32 n k
-    ba_hupd += itr * 32.0 * n * k;
-    b_hupd += itr * 8.0 * (k * n * (ns + 2.0) + k * k * (ns + 2.0) + k * KMAX);
-    b_lab += 8.0 * k * n + 4.0 * n;
-    cols += k;
-    if (out && out->iters) out->iters[rslot[rid]] = itr;
-    if (out && out->stopped_early) out->stopped_early[rslot[rid]] = (sr[rid] == 1 || sr[rid] == 3);
-  }
-  const double a_bytes = 8.0 * m * n;   // A, read once per launch by each contraction
-  if (const long long c = e->klaunch[KID_WTA]) {
-    e->kflops[KID_WTA] = fl_wta / c;
-    e->kbytes_algo[KID_WTA] = a_bytes + ba_wta / c;
-    e->kbytes[KID_WTA] = a_bytes + b_wta / c;
-  }
-  if (const long long c = e->klaunch[KID_AHTW]) {
-    e->kflops[KID_AHTW] = fl_ahtw / c;
-    e->kbytes_algo[KID_AHTW] = a_bytes + ba_ahtw / c;
-    e->kbytes[KID_AHTW] = a_bytes + b_ahtw / c;
-  }
-  if (const long long c = e->klaunch[KID_SMALL]) {   // the whole MU iteration in one persistent launch
-    e->kflops[KID_SMALL] = (fl_wta + fl_ahtw) / c;
-    e->kbytes_algo[KID_SMALL] = (ba_wta + ba_ahtw + ba_hupd) / c;
-    e->kbytes[KID_SMALL] = e->kbytes_algo[KID_SMALL];
-  }
-  if (const long long c = e->klaunch[KID_HUPD]) {
-    e->kbytes_algo[KID_HUPD] = ba_hupd / c;
-    e->kbytes[KID_HUPD] = b_hupd / c;
-  }
-  if (e->klaunch[KID_LABELS]) e->kbytes[KID_LABELS] = e->kbytes_algo[KID_LABELS] = b_lab;   // one launch
-  if (e->klaunch[KID_COUNTS]) {   // labels of each k group read once, n x n int32 counts written per k
-    e->kbytes_algo[KID_COUNTS] = 4.0 * nj * n + 4.0 * nk * n * n;
-    e->kbytes[KID_COUNTS] = e->kbytes_algo[KID_COUNTS];
-  }
-  (void)cols;
-
-  if (out && (out->W || out->H)) {
-    std::vector<long> woff(nj + 1, 0), ho(nj + 1, 0);
-    for (int s = 0; s < nj; ++s) {
-      woff[s + 1] = woff[s] + (long)m * job_k(s);
-      ho[s + 1] = ho[s] + (long)job_k(s) * n;
-    }
-    std::vector<double> hrow;
-    for (int rid = 0; rid < nj; ++rid) {
-      const int s = rslot[rid], k = all[rid].k;
-      if (out->W)
-        HCHECK(hipMemcpy2DAsync(out->W + woff[s], sizeof(double) * m, e->Wfin.as<double>() + (long)hoff[rid] * e->m_pad,
-                                sizeof(double) * e->m_pad, sizeof(double) * m, k, hipMemcpyDeviceToHost, st));
-      if (out->H) {
-        hrow.assign((size_t)k * n, 0.0);
-        HCHECK(hipMemcpy2DAsync(hrow.data(), sizeof(double) * n, e->Hfin.as<double>() + (long)hoff[rid] * e->n_pad,
-                                sizeof(double) * e->n_pad, sizeof(double) * n, k, hipMemcpyDeviceToHost, st));
-        HCHECK(hipStreamSynchronize(st));
-        for (int j = 0; j < n; ++j)
-          for (int a = 0; a < k; ++a) out->H[ho[s] + (long)j * k + a] = hrow[(size_t)a * n + j];
-      }
-    }
-    HCHECK(hipStreamSynchronize(st));
-  }
-  auto t_end = std::chrono::steady_clock::now();
+  // ---- results: archive, labels / counts / consensus, kernel accounting, factors ----
+  if (archive_rest(s) || labels_counts_consensus(s, out)) return -1;
+  account_kernels(s, out);
+  if (download_factors(s, out)) return -1;
+  const auto t_end = clk::now();
   if (out) {
     out->seconds_total = std::chrono::duration<double>(t_end - t_start).count();
     out->seconds_iterate = std::chrono::duration<double>(t_iter1 - t_iter0).count();
-    out->restart_iterations = tot_iters;
-    out->max_iter_run = max_it;
+    out->restart_iterations = s.tot_iters;
+    out->max_iter_run = s.max_it;
   }
-  if (opts.verbose) {
-    fprintf(stderr, "[nmfc] %d restarts, %d iterations enqueued, max %d, mean %.1f, %d repacks, %.3f s\n", nj,
-            iters_enqueued, max_it, (double)tot_iters / nj, e->repacks,
-            std::chrono::duration<double>(t_end - t_start).count());
+  if (s.opts.verbose) {
+    fprintf(stderr, "[nmfc] %d restarts, %d iterations enqueued, max %d, mean %.1f, %d repacks, %.3f s\n", s.nj, s.it,
+            s.max_it, (double)s.tot_iters / s.nj, e->repacks, std::chrono::duration<double>(t_end - t_start).count());
   }
   return 0;
 }
@@ -1469,7 +1673,7 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
 int nmfc_engine_mu1(nmfc_engine* e, int k, int maxiter, int stop_rule, const double* W0, const double* H0,
                     double* W_out, double* H_out, int* iters, int* early) {
   if (!e || !W0 || !H0 || !W_out || !H_out || maxiter < 0 || k < 1 || k > 16 || k > e->m || k > e->n ||
-      (stop_rule != NMFC_STOP_FIXED && stop_rule != NMFC_STOP_REF_COMPAT && stop_rule != NMFC_STOP_ARGMAX_STABLE)) {
+      !nmfc_mu_stop_rule_ok(stop_rule)) {
     set_err("nmfc_engine_mu1: bad arguments");
     return -1;
   }

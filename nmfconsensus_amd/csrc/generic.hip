@@ -17,9 +17,8 @@
 #include <vector>
 
 #include "../../include/nmfc.h"
+#include "nmfc_internal.hpp"
 #include "nmfc_kernels.hpp"
-
-void nmfc_set_error(const char* msg);
 
 namespace {
 
@@ -159,7 +158,7 @@ int fail(const char* what, hipError_t e) {
 extern "C" int nmfc_mu_generic(const double* A, int m, int n, int k, int maxiter, int stop_rule, double* W, double* H,
                                int* iters, int* early) {
   if (!A || !W || !H || m < 1 || n < 1 || k < 1 || k > m || k > n || maxiter < 0 ||
-      (stop_rule != NMFC_STOP_FIXED && stop_rule != NMFC_STOP_REF_COMPAT && stop_rule != NMFC_STOP_ARGMAX_STABLE)) {
+      !nmfc_mu_stop_rule_ok(stop_rule)) {
     nmfc_set_error("nmfc_mu_generic: bad arguments");
     return -1;
   }

@@ -28,9 +28,8 @@
 #include <vector>
 
 #include "../../include/nmfc.h"
+#include "nmfc_internal.hpp"
 #include "nmfc_kernels.hpp"
-
-void nmfc_set_error(const char* msg);
 
 namespace {
 
@@ -973,7 +972,7 @@ int mu_solo_call(const double* A, int m, int n, int k, int maxiter, int stop_rul
 extern "C" int nmfc_mu_solo(const double* A, int m, int n, int k, int maxiter, int stop_rule, const double* W0,
                             const double* H0, double* W, double* H, int* iters, int* early) {
   if (!A || !W0 || !H0 || !W || !H || !nmfc_mu_solo_fits(m, n, k) || maxiter < 0 ||
-      (stop_rule != NMFC_STOP_FIXED && stop_rule != NMFC_STOP_REF_COMPAT && stop_rule != NMFC_STOP_ARGMAX_STABLE)) {
+      !nmfc_mu_stop_rule_ok(stop_rule)) {
     nmfc_set_error("nmfc_mu_solo: bad arguments (needs 2 <= k <= 8, k <= m <= 1024, k <= n <= 40)");
     return -1;
   }

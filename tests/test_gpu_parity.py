@@ -275,9 +275,12 @@ def test_ragged_shapes_vs_oracle(oracle, m, n, ks):
 
 
 # 2 and 1 sample tiles of 128 (the Gram blocks spread differently); 4 and 16: the big tiles take their diagonal Gram
-# blocks from the W fragment registers (GTile GREG) while the other shapes stage them through LDS
-@pytest.mark.parametrize("n", [150, 100, 500, 2000])
-def test_tile_shapes_bit_identical(oracle, n):
+# blocks from the W fragment registers (GTile GREG) while the other shapes stage them through LDS.  R = 3 packs into 2
+# live panels, where the forced tiny tile always takes its 8-stage-ring instantiation (nsplit * live * 4 * ntj <= CUs);
+# n = 500 with R = 17 packs 595 columns into 11 live panels: 2 * 11 * 4 * 4 = 352 workgroups, the GT_NBUF-ring one
+@pytest.mark.parametrize("n,R", [(150, 3), (100, 3), (500, 3), (2000, 3), (500, 17)],
+                         ids=["150", "100", "500", "2000", "500-R17"])
+def test_tile_shapes_bit_identical(oracle, n, R):
     # every W^T A / A h^T tile shape the engine picks by grid size sums in the same canonical K order:
     # forcing each shape gives the same bits (so results never depend on how many restarts are live)
     import os
@@ -291,13 +294,13 @@ def test_tile_shapes_bit_identical(oracle, n):
             for ahtw in ("128", "64"):
                 os.environ["NMFC_WTA_TILE"], os.environ["NMFC_AHTW_TILE"] = wta, ahtw
                 with Engine(A) as eng:
-                    runs[(wta, ahtw)] = eng.run(ks, 3, maxiter=T, seed=5, stop_rule=0, want_factors=True)
+                    runs[(wta, ahtw)] = eng.run(ks, R, maxiter=T, seed=5, stop_rule=0, want_factors=True)
     finally:
         os.environ.pop("NMFC_WTA_TILE", None)
         os.environ.pop("NMFC_AHTW_TILE", None)
     ref = runs[("big", "128")]
     for key, r in runs.items():
-        for j in range(len(ks) * 3):
+        for j in range(len(ks) * R):
             assert np.array_equal(r.W[j], ref.W[j]) and np.array_equal(r.H[j], ref.H[j]), (key, j)
     W0, H0 = oracle.init_restart(5 + 3, m, n, 16)
     Wo, Ho, _ = oracle.nmf_mu(A, W0, H0, T, 0)
