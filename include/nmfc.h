@@ -223,6 +223,15 @@ double nmfc_engine_kernel_flops(nmfc_engine* e, int kernel_id);
  * split-K / Gram partials); *algo_bytes_out (may be NULL) receives the algorithmic bytes (each operand
  * once; the H update uses SURVEY 8(d)'s 32 n k per restart-iteration). */
 double nmfc_engine_kernel_bytes(nmfc_engine* e, int kernel_id, double* algo_bytes_out);
+/* Which schedule the last nmfc_engine_run took, "NAME=value;..." like nmfc_build_tuning (host counters; the string
+ * lives until the next call on this engine).  A job's results never depend on any of it; tests read it to know which
+ * paths a run exercised.  small: 1 when the small-shape kernels ran the sweep (no polls, repacks or per-form
+ * counts then); repacks / repacks_skipped: repacks done / put off because the new
+ * packing would not fit the buffers; polls: reads of the stop count enqueued; iterations_enqueued: MU iterations
+ * launched; panels_first / panels_min: 64-column panels (padded) of the first / the smallest packing;
+ * wta_narrow, wta_sk, wta_big, wta_mid, wta_small, wta_tiny: iterations launched per W^T A form (narrow tail kernel,
+ * stream-K, 4-panel, 2-panel, 1 x 64 and 1 x 32 tiles); ahtw_narrow, ahtw_128, ahtw_64: the same per A h^T form. */
+const char* nmfc_engine_run_info(nmfc_engine* e);
 
 #ifdef __cplusplus
 }

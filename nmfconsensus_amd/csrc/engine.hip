@@ -336,6 +336,13 @@ struct nmfc_engine {
   double kbytes[KID_N] = {0};       // bytes the kernel's design moves per launch (operands + partials)
   double kbytes_algo[KID_N] = {0};  // algorithmic bytes per launch (each operand once)
   int repacks = 0;
+  // nmfc_engine_run_info: which schedule the last run took (plain host counters, reset with repacks)
+  struct RunInfo {
+    int small = 0, repacks_skipped = 0, polls = 0, iterations_enqueued = 0, panels_first = 0, panels_min = 0;
+    long long wta_narrow = 0, wta_sk = 0, wta_big = 0, wta_mid = 0, wta_small = 0, wta_tiny = 0;   // iterations per W^T A form
+    long long ahtw_narrow = 0, ahtw_128 = 0, ahtw_64 = 0;                                         // ... per A h^T form
+  } info;
+  std::string info_str;
 };
 
 namespace {
@@ -733,6 +740,8 @@ int plan_jobs(Sweep& s) {
   s.pk = s.small ? pack_small(blk_jobs, s.sblocks) : pack(s.all);
   if (s.small && !solo_jobs.empty()) s.solo = place_solo(s.pk, solo_jobs, (int)s.sblocks.size() * 16, n);
   s.cap_cols = (long)s.pk.npanels * PANEL;
+  e->info.small = s.small;
+  e->info.panels_first = e->info.panels_min = s.pk.npanels;
   s.ntj = (int)(e->n_cols_pad / 128);
   s.g_ld = e->n_cols_pad;
   s.g_split = s.cap_cols * s.g_ld;
@@ -1029,6 +1038,7 @@ void launch_wta_narrow(const Sweep& s, int nblk) {
   const int ntq = (int)(e->n_cols_pad / 16);
   // loader / consumer waves (two waves), or the one-wave form: bit-identical
   auto kn = e->narrow_lc ? k_wta_narrow_lc<16, NARROW_NBUF, true> : k_wta_narrow<16, NARROW_NBUF, true>;
+  ++e->info.wta_narrow;
   hipLaunchKernelGGL(kn, dim3(e->nsplit * nblk * (ntq + 1)), dim3(e->narrow_lc ? 128 : 64), 0, e->st,
                      e->W[s.cur].as<double>(), e->Ablk.as<double>(), e->m_pad, ntq, e->nsplit, e->kchunk, nblk,
                      e->colinfo.as<ColInfo>(), e->Gpart.as<double>(), s.g_ld, s.g_split, e->SWpart.as<double>(),
@@ -1045,6 +1055,7 @@ int launch_wta_sk(Sweep& s, bool big, int ng, int* gsplit) {
     if (e->skfix.ensure(sizeof(double) * SK_FIX * e->ncu) || e->skflag.ensure(sizeof(unsigned) * e->ncu)) return -1;
     HCHECK(hipMemsetAsync(e->skflag.p, 0, sizeof(unsigned) * e->ncu, st));
   }
+  ++e->info.wta_sk;
   const long tiles = (long)ng * s.ntj;
   const bool lastsum = e->wta_lastsum && big;
   if (lastsum && e->sktcnt.bytes < sizeof(unsigned) * tiles) {
@@ -1074,6 +1085,7 @@ struct Wta2Launch {
   int ngroups;    // panel groups (of the tile's 4, 2 or 1 panels)
   int tiles;      // sample tiles per group
   int gram_wgs;   // the 1-panel shapes: Gram workgroups of their own per (chunk, group)
+  int tile;       // TileChoice::wta of the shape (run-info counters)
 };
 
 // W^T A on the GTile core: the instantiation and grid of tile shape `tile` (TileChoice::wta) for `live` panels holding
@@ -1089,7 +1101,7 @@ Wta2Launch pick_wta2(const nmfc_engine* e, int tile, int ntj, int live, int npan
                                             : k_wta2<WTA_NPT, 128, 4, 2, 1, GT_NBUF, 1, true, true, false, WTA_GREG>)
                     : (ntj >= 2) ? k_wta2<WTA_NPT, 128, 4, 2, 2, GT_NBUF, 1, true>
                                  : k_wta2<WTA_NPT, 128, 4, 2, 4, GT_NBUF, 1, true>;
-    return {kw, (ntj >= 4 && WTA_W16) ? 1024 : 512, npanels / WTA_NPT, ntj, 0};
+    return {kw, (ntj >= 4 && WTA_W16) ? 1024 : 512, npanels / WTA_NPT, ntj, 0, 0};
   }
   if (tile == 3) {   // npanels is a multiple of WTA_NPT, so of 2
     // ntj >= 4: wave rows = panels (2 x 4 waves, 64 x 32 outputs each) with every Gram chain in registers
@@ -1097,19 +1109,20 @@ Wta2Launch pick_wta2(const nmfc_engine* e, int tile, int ntj, int live, int npan
     Wta2Kernel kw = (ntj >= 4 && WTA_MID_GREG) ? k_wta2<2, 128, 2, 4, 1, WTA_MID_NBUF, WTA_MID_MINW, true, true, false, true>
                     : (ntj >= 2)               ? k_wta2<2, 128, 4, 2, 1, WTA_MID_NBUF, WTA_MID_MINW, true>
                                                : k_wta2<2, 128, 4, 2, 2, WTA_MID_NBUF, WTA_MID_MINW, true>;
-    return {kw, 512, (lp + 1) / 2, ntj, 0};
+    return {kw, 512, (lp + 1) / 2, ntj, 0, 3};
   }
   if (tile != 2)   // 1-panel tiles: the Gram blocks in 3 workgroups of their own per (chunk, panel)
-    return {k_wta2<1, 64, 2, 2, 1, GT_NBUF, 1, true, true, true>, 256, lp, 2 * ntj, 3};
+    return {k_wta2<1, 64, 2, 2, 1, GT_NBUF, 1, true, true, true>, 256, lp, 2 * ntj, 3, 1};
   // few live panels: 1-panel x 32-sample tiles, two 16x16 blocks per wave (short chains);
   // at most one live workgroup per CU: an 8-stage ring (more DMA in flight per CU, 96 KiB)
   Wta2Kernel kw = (long)e->nsplit * live * 4 * ntj <= e->ncu ? k_wta2<1, 32, 4, 1, 1, 8, 1, true, true, true>
                                                              : k_wta2<1, 32, 4, 1, 1, GT_NBUF, 1, true, true, true>;
-  return {kw, 256, lp, 4 * ntj, 3};
+  return {kw, 256, lp, 4 * ntj, 3, 2};
 }
 
 void launch_wta2(const Sweep& s, const Wta2Launch& l) {
   nmfc_engine* e = s.e;
+  ++(l.tile == 0 ? e->info.wta_big : l.tile == 3 ? e->info.wta_mid : l.tile == 1 ? e->info.wta_small : e->info.wta_tiny);
   hipLaunchKernelGGL(l.kern, dim3(e->nsplit * l.ngroups * (l.tiles + l.gram_wgs)), dim3(l.threads), 0, e->st,
                      e->W[s.cur].as<double>(), e->Ablk.as<double>(), e->m_pad, l.ngroups, l.tiles, e->nsplit, e->kchunk,
                      e->prb.as<int>(), e->pre.as<int>(), e->rinfo.as<RestartInfo>(), e->colinfo.as<ColInfo>(),
@@ -1151,6 +1164,7 @@ void launch_hupdate(const Sweep& s, int iter, int gsplit) {
 
 void launch_ahtw(const Sweep& s, const ChunkPlan& cp, int iter) {
   nmfc_engine* e = s.e;
+  ++(cp.nblk > 0 ? e->info.ahtw_narrow : cp.tc.ahtw_small ? e->info.ahtw_64 : e->info.ahtw_128);
   if (cp.nblk > 0)   // per live 16-column block: 16 rows x 32 genes, 2 waves
     hipLaunchKernelGGL((k_ahtw4<GT / 4, GT_NBUF, 1, 16, 2>), dim3(4 * e->ngt * cp.nblk), dim3(128), 0, e->st,
                        iter, e->H[s.cur].as<double>(), e->n_pad, e->Arm.as<double>(), e->m_pad,
@@ -1267,6 +1281,7 @@ int repack(Sweep& s, int stopped) {
     // first-fit decreasing is not monotone under removal: a (rare) larger packing would overrun
     // the buffers sized from the initial one, so keep the current placement until the next poll
     s.stopped_at_pack = stopped;
+    ++e->info.repacks_skipped;
     return 0;
   }
   std::vector<int> old_col(nj, -1);
@@ -1291,6 +1306,7 @@ int repack(Sweep& s, int stopped) {
   s.nact = (int)s.pk.ri.size();
   s.stopped_at_pack = nj - s.nact;
   ++e->repacks;
+  e->info.panels_min = std::min(e->info.panels_min, s.pk.npanels);
   return 0;
 }
 
@@ -1620,6 +1636,20 @@ double nmfc_engine_kernel_bytes(nmfc_engine* e, int kid, double* algo_bytes_out)
   return e->kbytes[kid];
 }
 
+const char* nmfc_engine_run_info(nmfc_engine* e) {
+  if (!e) return "";
+  const nmfc_engine::RunInfo& i = e->info;
+  char buf[640];
+  snprintf(buf, sizeof buf,
+           "small=%d;repacks=%d;repacks_skipped=%d;polls=%d;iterations_enqueued=%d;panels_first=%d;panels_min=%d;"
+           "wta_narrow=%lld;wta_sk=%lld;wta_big=%lld;wta_mid=%lld;wta_small=%lld;wta_tiny=%lld;"
+           "ahtw_narrow=%lld;ahtw_128=%lld;ahtw_64=%lld",
+           i.small, e->repacks, i.repacks_skipped, i.polls, i.iterations_enqueued, i.panels_first, i.panels_min,
+           i.wta_narrow, i.wta_sk, i.wta_big, i.wta_mid, i.wta_small, i.wta_tiny, i.ahtw_narrow, i.ahtw_128, i.ahtw_64);
+  e->info_str = buf;
+  return e->info_str.c_str();
+}
+
 int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_sweep_opts* opts_in,
                     const double* W_init, const double* H_init, nmfc_result* out) {
   using clk = std::chrono::steady_clock;
@@ -1635,6 +1665,7 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
     e->kbytes_algo[x] = 0;
   }
   e->repacks = 0;
+  e->info = nmfc_engine::RunInfo();
   s.want_w = out && out->W;
   if (plan_jobs(s) || ensure_buffers(s)) return -1;
   if (W_init && H_init ? init_from_caller(s, W_init, H_init)
@@ -1646,6 +1677,8 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
   if (s.small ? small_phase(s) : mfma_loop(s)) return -1;
   HCHECK(hipStreamSynchronize(e->st));
   if (e->timing) drain_timing(e);
+  e->info.polls = s.polls;
+  e->info.iterations_enqueued = s.it;
   const auto t_iter1 = clk::now();
 
   // ---- results: archive, labels / counts / consensus, kernel accounting, factors ----
@@ -1660,8 +1693,8 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
     out->max_iter_run = s.max_it;
   }
   if (s.opts.verbose) {
-    fprintf(stderr, "[nmfc] %d restarts, %d iterations enqueued, max %d, mean %.1f, %d repacks, %.3f s\n", s.nj, s.it,
-            s.max_it, (double)s.tot_iters / s.nj, e->repacks, std::chrono::duration<double>(t_end - t_start).count());
+    fprintf(stderr, "[nmfc] %d restarts, %d iterations enqueued, max %d, mean %.1f, %d repacks, %.3f s\n", s.nj,
+            e->info.iterations_enqueued, s.max_it, (double)s.tot_iters / s.nj, e->repacks, std::chrono::duration<double>(t_end - t_start).count());
   }
   return 0;
 }

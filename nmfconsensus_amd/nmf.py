@@ -139,6 +139,12 @@ class Engine:
         b = self.L.nmfc_engine_kernel_bytes(self.h, kid, ctypes.byref(algo))
         return b, algo.value
 
+    def last_run_info(self) -> dict[str, int]:
+        """Which schedule the last run() took (nmfc_engine_run_info): repacks, polls, panels, and the iterations
+        launched per W^T A / A h^T kernel form.  Results never depend on it; tests read it to see what ran."""
+        txt = self.L.nmfc_engine_run_info(self.h).decode()
+        return {k: int(v) for k, v in (kv.split("=", 1) for kv in txt.split(";") if kv)}
+
     def mu1(self, W0, H0, *, maxiter: int = 10000, stop_rule: int = STOP_REF_COMPAT):
         """One restart from caller factors (W0 m x k, H0 k x n) on the small-shape team kernel: the per-call path
         of the nmf_mu drop-in (nmfc_engine_mu1; m rounded up to 128 <= 1024, n <= 64).  Returns (W, H, iters,
