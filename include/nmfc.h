@@ -99,6 +99,25 @@ void nmfc_default_opts(nmfc_sweep_opts* o);
 int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_sweep_opts* opts,
                     const double* W_init, const double* H_init, nmfc_result* out);
 
+/* enable != 0: later nmfc_engine_run calls keep every shard job's final W in the device archive (as they do when
+ * out->W is given) and compute each job's residual norm in the results phase (one batched pass over the archive: A is
+ * read once per group of restarts, no m x n difference matrix is written, two launches whatever the job count).
+ * Default 0: runs are exactly as before. */
+void nmfc_engine_set_residuals(nmfc_engine* e, int enable);
+
+/* After a run with residuals enabled: dnorm_out[j - job_begin] = ||A - W_j H_j||_F / sqrt(m n), the value
+ * calculateNorm (calculatenorm.c:44-78) gives for the job's final factors.  A job's value depends on (m, n, k, W_j,
+ * H_j) only: not on the shard, the batch or the GPU count.  Returns the number of jobs written, or -1
+ * (nmfc_last_error) when the last run on this engine had residuals disabled or failed. */
+int nmfc_engine_residuals(nmfc_engine* e, double* dnorm_out);
+
+/* Best restart per rank of the last run's shard: best_job_out[g] = global 0-based job id of the job of ks[g] with
+ * the smallest dnorm (the lowest job id on ties; -1 when the shard holds no job of ks[g]); best_dnorm_out[g] its
+ * dnorm (NaN for a -1 entry).  W_out / H_out (either may be NULL, as may the other two): those jobs' factors,
+ * k-index-major, W m x k and H k x n column-major (nothing written for a -1 entry, whose space is skipped).  Only
+ * these nk jobs are copied off the device.  Returns nk, or -1 as nmfc_engine_residuals. */
+int nmfc_engine_best(nmfc_engine* e, int32_t* best_job_out, double* best_dnorm_out, double* W_out, double* H_out);
+
 /* Convenience: create, run, destroy. */
 /* One restart of nmf_mu (nmf_mu.c:84-315) on the small-shape team kernel (m rounded up to 128 <= 8192, n <= 64,
  * k <= 16), with one upload, one launch and one download: the per-call path of the nmf_mu drop-in (nmf.r:41-45).
@@ -210,7 +229,9 @@ const char* nmfc_version(void);
  * engine's stream: kernel ids 0 = wta (W^T A + W^T W, MFMA), 1 = hupdate (H update + stop check),
  * 2 = ahtw (A h^T MFMA + W update), 3 = init, 4 = other (repack moves, TolX W check), 5 = labels,
  * 6 = connectivity counts, 7 = small-shape persistent MU kernel (m_pad <= 1024, n <= 64: the whole
- * loop in one launch).  Returns the number of launches of that kernel. */
+ * loop in one launch), 8 = the residual pass (k_resid + k_resid_sum as one timed scope; only with
+ * nmfc_engine_set_residuals; its flop figure counts (2k + 3) m n fp64 operations per job).  Returns the number of
+ * launches of that kernel. */
 long long nmfc_engine_kernel_time(nmfc_engine* e, int kernel_id, double* ms_out);
 /* enable = 0: no event timing; enable = S >= 1: HIP events around every launch of every S-th MU
  * iteration (and every other launch), so kernel_time returns the TIMED launches and their summed ms

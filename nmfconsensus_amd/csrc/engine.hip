@@ -118,7 +118,7 @@ std::vector<uint32_t> make_jump_table(int nchunks, int rchunk) {
   return table;
 }
 
-enum { KID_WTA = 0, KID_HUPD = 1, KID_AHTW = 2, KID_INIT = 3, KID_OTHER = 4, KID_LABELS = 5, KID_COUNTS = 6, KID_SMALL = 7, KID_N = 8 };
+enum { KID_WTA = 0, KID_HUPD = 1, KID_AHTW = 2, KID_INIT = 3, KID_OTHER = 4, KID_LABELS = 5, KID_COUNTS = 6, KID_SMALL = 7, KID_RESID = 8, KID_N = 9 };
 
 // Packing of a restart list: first-fit decreasing (k descending, ties by rid) into 16-column blocks -- a restart
 // never straddles a block -- and blocks, in order, four to a 64-column panel; panel count rounded up to a
@@ -343,6 +343,14 @@ struct nmfc_engine {
     long long ahtw_narrow = 0, ahtw_128 = 0, ahtw_64 = 0;                                         // ... per A h^T form
   } info;
   std::string info_str;
+  // nmfc_engine_set_residuals: the residual pass of the results phase.  ssq: sum of d^2 per shard job of the last
+  // run (device, and h_ssq on the host); respart: its per-(job, tile) partials.  last_*: what the getters need of that
+  // run (the archive Wfin / Hfin lives until the next one): the shard, and each shard job's first archive row
+  bool residuals = false, resid_valid = false;
+  DevBuf ssq, respart;
+  std::vector<double> h_ssq;
+  std::vector<int> last_ks, last_row;
+  long last_jb = 0;
 };
 
 namespace {
@@ -633,6 +641,7 @@ struct Sweep {
   PollEvents pe;
   long long tot_iters = 0;          // accounting: restart-iterations run, and the longest restart
   int max_it = 0;
+  std::vector<RestartInfo> fin;     // residual pass: by rid, the archive rows (alive until the run's last synchronisation)
   int job_k(int s) const { return ks[(jb + s) % nk]; }
 };
 
@@ -1331,6 +1340,50 @@ int mfma_loop(Sweep& s) {
   return 0;
 }
 
+// The residual pass (nmfc_engine_set_residuals): the sum of d^2 of every job from the archive, two launches whatever
+// the job count, stream-ordered behind the archive moves; the labels phase's synchronisation completes the host copy.
+int residual_pass(Sweep& s) {
+  nmfc_engine* e = s.e;
+  if (!e->residuals) return 0;
+  hipStream_t st = e->st;
+  const int nj = s.nj;
+  const int nst = (e->n + RES_ST - 1) / RES_ST, ntiles = (e->m + RES_GT - 1) / RES_GT * nst;
+  const int ngroups = (nj + RES_JG - 1) / RES_JG;
+  if (ngroups > 65535) {
+    set_err("nmfc_engine_run: residuals of %d jobs exceed the residual pass's grid", nj);
+    return -1;
+  }
+  if (e->ssq.ensure(sizeof(double) * nj) || e->respart.ensure(sizeof(double) * (size_t)nj * ntiles)) return -1;
+  s.fin.resize(nj);
+  for (int rid = 0; rid < nj; ++rid) s.fin[rid] = {s.hoff[rid], s.all[rid].k, rid, s.all[rid].sq_off};
+  HCHECK(hipMemcpyAsync(e->finfo.p, s.fin.data(), sizeof(RestartInfo) * nj, hipMemcpyHostToDevice, st));
+  {
+    TimedLaunch tl(e, KID_RESID);
+    hipLaunchKernelGGL(k_resid, dim3(ntiles, ngroups), dim3(NT), 0, st, e->finfo.as<RestartInfo>(), nj,
+                       e->Ablk.as<double>(), e->n_cols_pad, e->Wfin.as<double>(), e->m_pad, e->Hfin.as<double>(), e->n_pad,
+                       e->m, e->n, nst, e->respart.as<double>());
+    hipLaunchKernelGGL(k_resid_sum, dim3(nj), dim3(64), 0, st, e->respart.as<double>(), ntiles, e->slot.as<int>(),
+                       e->ssq.as<double>());
+  }
+  HCHECK(hipGetLastError());
+  e->h_ssq.assign(nj, 0.0);
+  HCHECK(hipMemcpyAsync(e->h_ssq.data(), e->ssq.p, sizeof(double) * nj, hipMemcpyDeviceToHost, st));
+  // accounting (one launch pair): (2k + 3) m n lane operations per job; A once per group of RES_JG restarts, a job's W
+  // once per sample tile and H once per gene tile, the partials written and read (algorithmic: each operand once)
+  double fl = 0, bw = 0, bh = 0;
+  for (int rid = 0; rid < nj; ++rid) {
+    const double k = s.all[rid].k;
+    fl += (2.0 * k + 3.0) * e->m * e->n;
+    bw += 8.0 * k * e->m;
+    bh += 8.0 * k * e->n;
+  }
+  const double a_bytes = 8.0 * e->m * e->n;
+  e->kflops[KID_RESID] = fl;
+  e->kbytes_algo[KID_RESID] = a_bytes + bw + bh + 8.0 * nj;
+  e->kbytes[KID_RESID] = a_bytes * ngroups + bw * nst + bh * (ntiles / nst) + 16.0 * nj * ntiles + 8.0 * nj;
+  return 0;
+}
+
 // Labels of every restart from the archive, the co-clustering counts and consensus per k when asked for, and the stop
 // state back on the host (si, sr).
 int labels_counts_consensus(Sweep& s, nmfc_result* out) {
@@ -1619,6 +1672,75 @@ void nmfc_engine_set_timing(nmfc_engine* e, int enable) {
   e->timing_stride = std::max(1, enable);
 }
 
+void nmfc_engine_set_residuals(nmfc_engine* e, int enable) {
+  if (e) e->residuals = enable != 0;
+}
+
+namespace {
+// the last run's sum of d^2 as calculateNorm's value (the expression of nmfc_calculate_norm_dev)
+double resid_norm(const nmfc_engine* e, int slot) { return sqrt(e->h_ssq[slot]) / sqrt((double)e->m * e->n); }
+
+int resid_ready(const nmfc_engine* e, const char* who) {
+  if (!e) {
+    set_err("%s: no engine", who);
+    return -1;
+  }
+  if (!e->resid_valid) {
+    set_err("%s: the last run on this engine had residuals disabled or failed (nmfc_engine_set_residuals)", who);
+    return -1;
+  }
+  return 0;
+}
+}  // namespace
+
+int nmfc_engine_residuals(nmfc_engine* e, double* dnorm_out) {
+  if (resid_ready(e, "nmfc_engine_residuals")) return -1;
+  if (!dnorm_out) {
+    set_err("nmfc_engine_residuals: dnorm_out is NULL");
+    return -1;
+  }
+  const int nj = (int)e->h_ssq.size();
+  for (int j = 0; j < nj; ++j) dnorm_out[j] = resid_norm(e, j);
+  return nj;
+}
+
+int nmfc_engine_best(nmfc_engine* e, int32_t* best_job_out, double* best_dnorm_out, double* W_out, double* H_out) {
+  if (resid_ready(e, "nmfc_engine_best")) return -1;
+  const int nk = (int)e->last_ks.size(), nj = (int)e->h_ssq.size(), m = e->m, n = e->n;
+  std::vector<int> best(nk, -1);
+  std::vector<double> bd(nk, NAN);
+  for (int j = 0; j < nj; ++j) {   // ascending job id: a tie keeps the lower one
+    const int g = (int)((e->last_jb + j) % nk);
+    const double d = resid_norm(e, j);
+    if (best[g] < 0 || d < bd[g]) {
+      best[g] = j;
+      bd[g] = d;
+    }
+  }
+  if (W_out || H_out) HCHECK(hipSetDevice(e->dev));
+  std::vector<double> hrow;
+  long woff = 0, hoff = 0;
+  for (int g = 0; g < nk; ++g) {
+    const int k = e->last_ks[g], j = best[g];
+    if (best_job_out) best_job_out[g] = j < 0 ? -1 : (int32_t)(e->last_jb + j);
+    if (best_dnorm_out) best_dnorm_out[g] = bd[g];
+    if (j >= 0 && W_out)
+      HCHECK(hipMemcpy2DAsync(W_out + woff, sizeof(double) * m, e->Wfin.as<double>() + (long)e->last_row[j] * e->m_pad,
+                              sizeof(double) * e->m_pad, sizeof(double) * m, k, hipMemcpyDeviceToHost, e->st));
+    if (j >= 0 && H_out) {
+      hrow.assign((size_t)k * n, 0.0);
+      HCHECK(hipMemcpy2DAsync(hrow.data(), sizeof(double) * n, e->Hfin.as<double>() + (long)e->last_row[j] * e->n_pad,
+                              sizeof(double) * e->n_pad, sizeof(double) * n, k, hipMemcpyDeviceToHost, e->st));
+      HCHECK(hipStreamSynchronize(e->st));
+      transpose(hrow.data(), k, n, H_out + hoff);
+    }
+    woff += (long)m * k;
+    hoff += (long)k * n;
+  }
+  HCHECK(hipStreamSynchronize(e->st));
+  return nk;
+}
+
 long long nmfc_engine_kernel_time(nmfc_engine* e, int kid, double* ms_out) {
   if (!e || kid < 0 || kid >= KID_N) return -1;
   if (ms_out) *ms_out = e->kms[kid];
@@ -1654,6 +1776,7 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
                     const double* W_init, const double* H_init, nmfc_result* out) {
   using clk = std::chrono::steady_clock;
   Sweep s;
+  if (e) e->resid_valid = false;   // until this run has filled them
   if (check_args(s, e, ks, nk, R, opts_in)) return -1;
   const auto t_start = clk::now();
   for (int x = 0; x < KID_N; ++x) {
@@ -1666,7 +1789,7 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
   }
   e->repacks = 0;
   e->info = nmfc_engine::RunInfo();
-  s.want_w = out && out->W;
+  s.want_w = (out && out->W) || e->residuals;
   if (plan_jobs(s) || ensure_buffers(s)) return -1;
   if (W_init && H_init ? init_from_caller(s, W_init, H_init)
                        : s.opts.init_stream == NMFC_INIT_R_RUNIF ? init_r_runif(s) : init_glibc(s))
@@ -1682,9 +1805,16 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
   const auto t_iter1 = clk::now();
 
   // ---- results: archive, labels / counts / consensus, kernel accounting, factors ----
-  if (archive_rest(s) || labels_counts_consensus(s, out)) return -1;
+  if (archive_rest(s) || residual_pass(s) || labels_counts_consensus(s, out)) return -1;
   account_kernels(s, out);
   if (download_factors(s, out)) return -1;
+  if (e->residuals) {   // what nmfc_engine_residuals / nmfc_engine_best read of this run
+    e->last_ks.assign(ks, ks + nk);
+    e->last_jb = s.jb;
+    e->last_row.assign(s.nj, 0);
+    for (int rid = 0; rid < s.nj; ++rid) e->last_row[s.rslot[rid]] = s.hoff[rid];
+    e->resid_valid = true;
+  }
   const auto t_end = clk::now();
   if (out) {
     out->seconds_total = std::chrono::duration<double>(t_end - t_start).count();

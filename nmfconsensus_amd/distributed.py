@@ -101,8 +101,22 @@ def _counts_for(engine, nk, n, counts_tensor):
     return counts_tensor
 
 
+def merge_best(parts):
+    """The per-rank best restarts of several shards as one: per k the entry with the smallest (dnorm, job id), which
+    is what one unsharded run reports (a job's dnorm does not depend on its shard).  None when no part carries one."""
+    if all(p.best is None for p in parts):
+        return None
+    best = {}
+    for p in parts:
+        for k, b in (p.best or {}).items():
+            if k not in best or (b["dnorm"], b["job"]) < (best[k]["dnorm"], best[k]["job"]):
+                best[k] = b
+    return best
+
+
 def merge_results(parts):
-    """The SweepResults of contiguous sub-shards, in job order, as one SweepResult (counts left to the caller)."""
+    """The SweepResults of contiguous sub-shards, in job order, as one SweepResult (counts left to the caller).
+    dnorm is concatenated like the other per-job arrays; best is merged per k by (dnorm, job id) (merge_best)."""
     from .nmf import SweepResult
 
     if len(parts) == 1:
@@ -117,7 +131,8 @@ def merge_results(parts):
                        seconds_iterate=max(p.seconds_iterate for p in parts),
                        restart_iterations=sum(p.restart_iterations for p in parts),
                        max_iter_run=max(p.max_iter_run for p in parts), job_begin=p0.job_begin,
-                       job_end=parts[-1].job_end, extras={"groups": len(parts)})
+                       job_end=parts[-1].job_end, extras={"groups": len(parts)},
+                       dnorm=cat("dnorm") if all(p.dnorm is not None for p in parts) else None, best=merge_best(parts))
 
 
 class RestartGroups:
@@ -193,7 +208,8 @@ class RestartGroups:
     def run(self, ks, R: int, *, job_begin: int = 0, job_end: int = -1, counts_tensor=None, **kw):
         """Engine.run over [job_begin, job_end) as G groups.  counts_tensor (torch int32 (nk, n, n) on this
         GPU, optional): receives the shard's counts, summed over the groups on the device; otherwise the
-        result carries host counts/consensus when kw asks for them (Engine.run's want_counts)."""
+        result carries host counts/consensus when kw asks for them (Engine.run's want_counts).  want_residuals /
+        want_best pass through to every group: dnorm comes back in job order, best merged over the groups."""
         import torch
 
         if "counts_device_ptr" in kw:
@@ -252,7 +268,10 @@ def run_sharded(engine, ks, R: int, *, rank: int, world: int, unit: str = "job",
     None.  The engine's run returns after its stream has finished writing the counts, so the all-reduce
     (queued on torch's stream) reads complete data.  The all-reduce runs when reduce is set and either
     world > 1 or a process group is initialised (so a world-size-1 RCCL group exercises the collective).
-    Returns (counts_tensor_after_allreduce, local SweepResult)."""
+    Returns (counts_tensor_after_allreduce, local SweepResult).  want_residuals / want_best (MU engine) pass through
+    to the engine's run: the local result carries this rank's per-job dnorm and its rank-local best.  best is NOT
+    reduced across ranks here; gather the ranks' results and merge_results / merge_best them (per k the smallest
+    (dnorm, job id)) for the best of the whole sweep."""
     nk = len(ks)
     counts_tensor = _counts_for(engine, nk, engine.n, counts_tensor)
     if unit == "job":

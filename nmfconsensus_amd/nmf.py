@@ -80,6 +80,8 @@ class SweepResult:
     job_begin: int = 0
     job_end: int = 0
     extras: dict = field(default_factory=dict)
+    dnorm: np.ndarray | None = None    # (njobs,) float64: ||A - W_j H_j||_F / sqrt(m n) (want_residuals)
+    best: dict | None = None           # {k: dict(job=<global 0-based id>, dnorm=, W=<m x k>, H=<k x n>)} (want_best)
 
 
 class Engine:
@@ -102,7 +104,9 @@ class Engine:
             raise RuntimeError(f"nmfc_engine_create failed: {_lib.last_error()}")
         self.h = h
         self.m, self.n = m, n
+        self._last_ks, self._last_nj = [], 0
         self.device = self.L.nmfc_engine_device(h)   # HIP ordinal resolved at creation (device -1: the current one)
+        self._residuals = False
 
     def close(self):
         if getattr(self, "h", None):
@@ -124,6 +128,41 @@ class Engine:
     def set_timing(self, on: bool, stride: int = 1):
         """Event-time the launches of every `stride`-th MU iteration (nmfc_engine_set_timing)."""
         self.L.nmfc_engine_set_timing(self.h, max(1, int(stride)) if on else 0)
+
+    def set_residuals(self, on: bool):
+        """Later run() calls compute every job's residual norm in the results phase (nmfc_engine_set_residuals)."""
+        self._residuals = bool(on)
+        self.L.nmfc_engine_set_residuals(self.h, 1 if on else 0)
+
+    def residuals(self) -> np.ndarray:
+        """dnorm of every shard job of the last run, which must have had residuals enabled (nmfc_engine_residuals)."""
+        out = np.zeros(max(1, self._last_nj), dtype=np.float64)
+        got = self.L.nmfc_engine_residuals(self.h, out.ctypes.data_as(_dp))
+        if got < 0:
+            raise RuntimeError(f"nmfc_engine_residuals failed: {_lib.last_error()}")
+        return out[:got]
+
+    def best(self) -> dict:
+        """The best restart (smallest dnorm, lowest job id on ties) of every rank the last run's shard holds, with its
+        factors (nmfc_engine_best): {k: dict(job=, dnorm=, W=, H=)}.  Only these jobs' factors leave the device."""
+        ks, m, n = self._last_ks, self.m, self.n
+        nk = len(ks)
+        job = np.zeros(nk, dtype=np.int32)
+        dn = np.zeros(nk, dtype=np.float64)
+        wflat = np.zeros(sum(m * k for k in ks), dtype=np.float64)
+        hflat = np.zeros(sum(k * n for k in ks), dtype=np.float64)
+        if self.L.nmfc_engine_best(self.h, job.ctypes.data_as(_ip), dn.ctypes.data_as(_dp), wflat.ctypes.data_as(_dp),
+                                   hflat.ctypes.data_as(_dp)) < 0:
+            raise RuntimeError(f"nmfc_engine_best failed: {_lib.last_error()}")
+        out = {}
+        wo = ho = 0
+        for g, k in enumerate(ks):
+            if job[g] >= 0:
+                out[k] = dict(job=int(job[g]), dnorm=float(dn[g]), W=wflat[wo:wo + m * k].reshape((m, k), order="F"),
+                              H=hflat[ho:ho + k * n].reshape((k, n), order="F"))
+            wo += m * k
+            ho += k * n
+        return out
 
     def kernel_time(self, kid: int):
         ms = ctypes.c_double(0.0)
@@ -166,9 +205,15 @@ class Engine:
             label_rule: int = LABEL_ARGMAX, job_begin: int = 0, job_end: int = -1, W_init=None, H_init=None,
             want_factors: bool = False, want_counts: bool = True, counts_device_ptr: int | None = None,
             check_every: int = 4, min_init: int = 0, max_init: int = 1, verbose: bool = False,
-            TolX: float = 1e-4, TolFun: float = 1e-4, init_stream: int = INIT_LIBNMF, want_h: bool = False) -> SweepResult:
+            TolX: float = 1e-4, TolFun: float = 1e-4, init_stream: int = INIT_LIBNMF, want_h: bool = False,
+            want_residuals: bool = False, want_best: bool = False) -> SweepResult:
         """One sweep of the (k, restart) job grid (or its shard [job_begin, job_end)).  want_factors: final W and
-        H of every job; want_h: final H only (the C3-sized checks: W of 1800 jobs is 1.7 GB of host memory)."""
+        H of every job; want_h: final H only (the C3-sized checks: W of 1800 jobs is 1.7 GB of host memory).
+        want_residuals: SweepResult.dnorm, every job's ||A - W H||_F / sqrt(m n), from one batched pass on the device
+        (no factor download); want_best (implies want_residuals): SweepResult.best, per rank of the shard the restart
+        with the smallest dnorm and its W, H -- the only factors that leave the device.  Both are enabled for this
+        call only; the engine's set_residuals() setting (which, when on, fills dnorm on every run) is restored
+        afterwards."""
         ks = [int(k) for k in ks]
         nk = len(ks)
         njobs_all = nk * R
@@ -218,11 +263,22 @@ class Engine:
             if wi.size != sum(m * k for k in jk) or hi.size != sum(k * n for k in jk):
                 raise ValueError("W_init/H_init sizes do not match the job shard")
         ks_arr = np.array(ks, dtype=np.int32)
-        rc = self.L.nmfc_engine_run(self.h, ks_arr.ctypes.data_as(_ip), nk, R, ctypes.byref(o),
-                                    wi.ctypes.data_as(_dp) if wi is not None else None,
-                                    hi.ctypes.data_as(_dp) if hi is not None else None, ctypes.byref(res))
+        prev = self._residuals
+        want_residuals = want_residuals or want_best or prev
+        if want_residuals != prev:
+            self.set_residuals(want_residuals)
+        try:
+            rc = self.L.nmfc_engine_run(self.h, ks_arr.ctypes.data_as(_ip), nk, R, ctypes.byref(o),
+                                        wi.ctypes.data_as(_dp) if wi is not None else None,
+                                        hi.ctypes.data_as(_dp) if hi is not None else None, ctypes.byref(res))
+        finally:
+            if want_residuals != prev:
+                self.set_residuals(prev)
         if rc != 0:
             raise RuntimeError(f"nmfc_engine_run failed: {_lib.last_error()}")
+        self._last_ks, self._last_nj = ks, nj
+        dnorm = self.residuals() if want_residuals else None
+        best = self.best() if want_best else None
         Ws = Hs = None
         if want_factors or want_h:
             Ws = [] if want_factors else None
@@ -237,7 +293,7 @@ class Engine:
         return SweepResult(ks=ks, R=R, n=n, counts=counts, consensus=consensus, labels=labels, iters=iters,
                            stopped_early=early, W=Ws, H=Hs, seconds_total=res.seconds_total,
                            seconds_iterate=res.seconds_iterate, restart_iterations=res.restart_iterations,
-                           max_iter_run=res.max_iter_run, job_begin=jb, job_end=je)
+                           max_iter_run=res.max_iter_run, job_begin=jb, job_end=je, dnorm=dnorm, best=best)
 
 
 _DONMF = {"A": None, "eng": None, "device": None}
@@ -313,11 +369,14 @@ def createJobArray(A, k, num_clusterings: int, maxniter: int, seed: int, toleran
 
 def runNMFinJobs(A, k, num_clusterings: int, maxniter: int, seed: int, njobs: int = 1, *,
                  stop_rule: int = STOP_REF_COMPAT, label_rule: int = LABEL_ARGMAX, save_dir: str | None = None,
-                 device: int = -1, init_stream: int = INIT_LIBNMF):
+                 device: int = -1, init_stream: int = INIT_LIBNMF, want_best: bool = False):
     """nmf.r:106-119: run every (k, restart) job, reduce per k to a consensus matrix, then cophenetic,
     ordering and membership (computeConsensusAndSaveFiles).  `njobs` (BatchJobs chunks) has no effect:
     all jobs run as one batched sweep on the GPU (use nmfconsensus_amd.distributed for several GPUs).
-    Returns the dict produced by computeConsensusAndSaveFiles, plus the raw SweepResult under 'sweep'."""
+    Returns the dict produced by computeConsensusAndSaveFiles, plus the raw SweepResult under 'sweep'.
+    want_best: also 'best', {k: dict(job, dnorm, W, H)}: per rank the restart with the smallest residual norm and its
+    metagenes (the restart nmf.r:200-203's commented-out "Example H matrix" plots would show), and 'dnorm', every job's
+    residual norm in job order."""
     del njobs
     ks = list(k)
     if 1 in ks:
@@ -325,10 +384,12 @@ def runNMFinJobs(A, k, num_clusterings: int, maxniter: int, seed: int, njobs: in
     reg = createJobArray(A, ks, num_clusterings, maxniter, seed)
     with Engine(reg.A, device) as eng:
         sw = eng.run(ks, num_clusterings, maxiter=maxniter, seed=seed, stop_rule=stop_rule, label_rule=label_rule,
-                     init_stream=init_stream)
+                     init_stream=init_stream, want_best=want_best)
     result = {str(kk): sw.consensus[i] for i, kk in enumerate(ks)}
     out = computeConsensusAndSaveFiles(result, save_dir=save_dir)
     out["sweep"] = sw
+    if want_best:
+        out["best"], out["dnorm"] = sw.best, sw.dnorm
     return out
 
 
