@@ -199,8 +199,34 @@ int nmfc_brunet_run(nmfc_brunet* e, const int* ks, int nk, int R, const nmfc_bru
                     const double* H_init, nmfc_result* out);
 void nmfc_brunet_set_timing(nmfc_brunet* e, int enable);
 /* kernel ids 0 = H-side quotient product (k_br_hnum), 1 = H update + check (k_br_hupd), 2 = W side
- * (k_br_wupd); returns launches, fills accumulated event ms and algorithmic flop per launch. */
+ * (k_br_wupd), 3 = the divergence pass (k_br_div + k_br_div_sum as one timed scope per k batch; only with
+ * nmfc_brunet_set_divergence; priced at 2k + 6 + 83 lane-operations per element and restart, 83 being the device
+ * log's VALU instructions); returns launches, fills accumulated event ms and algorithmic flop per launch. */
 long long nmfc_brunet_kernel_time(nmfc_brunet* e, int kernel_id, double* ms_out, double* flops_per_launch);
+
+/* enable != 0: later nmfc_brunet_run calls also evaluate, once per job and on the factors the run returns, NMF.div's
+ * error.v figure  D = sum_{i,c} (a log((a + eps) / (p + eps)) - a + p) / (m n),  p = (W H)[i,c], eps = 2^-52
+ * (.Machine$double.eps), in one batched device pass per k batch (A read once per batch, no m x n intermediate), and
+ * keep per k the factors of the restart with the smallest D on the device.  Default 0: no launch, no buffer, runs
+ * exactly as before. */
+void nmfc_brunet_set_divergence(nmfc_brunet* e, int enable);
+
+/* After a run with the divergence enabled: div_out[(k index) * (restart_end - restart_begin) + (i - 1 - restart_begin)]
+ * = D of that job, the indexing of the other per-job outputs.  A job's value depends on (m, n, k, W_j, H_j) only: not
+ * on the batch, the restart groups, the lane, the shard or the GPU count.  Returns the number of values written, or -1
+ * (nmfc_last_error) when the last run on this engine had the divergence disabled or failed. */
+int nmfc_brunet_divergence(nmfc_brunet* e, double* div_out);
+
+/* Best restart per k of the last run's shard: best_restart_out[g] = the 0-based restart (i - 1, counted over all R
+ * restarts) of ks[g] with the smallest D, the lowest restart on ties; best_div_out[g] its D.  W_out / H_out: those
+ * jobs' factors, k-index-major, W m x k and H k x n column-major.  Any of the four pointers may be NULL.  Only these
+ * nk jobs' factors are copied off the device.  Returns nk, or -1 as nmfc_brunet_divergence (nothing is written then;
+ * a run over an empty restart range fails, so a shard without restarts answers -1 here). */
+int nmfc_brunet_best(nmfc_brunet* e, int32_t* best_restart_out, double* best_div_out, double* W_out, double* H_out);
+
+/* Diagnostic: y[i] = log(x[i]) for count host values by the device log the divergence pass calls, so that its error
+ * can be measured against a long-double log (the divergence bound of tests/kl_bound.py assumes 2 ulp).  0 or -1. */
+int nmfc_brunet_log_probe(nmfc_brunet* e, const double* x, int count, double* y);
 
 /* calculateNorm (calculatenorm.c:44-78) and calculateMaxchange (calculatemaxchange.c:42-71) on
  * DEVICE-resident column-major operands (e.g. torch tensors) on the current HIP device: d = a - w h and

@@ -40,7 +40,7 @@ class BrunetOpts(ctypes.Structure):
                 ("restart_begin", c_int), ("restart_end", c_int), ("verbose", c_int), ("lanes", c_int)]
 
 
-BK_HNUM, BK_HUPD, BK_WUPD = 0, 1, 2
+BK_HNUM, BK_HUPD, BK_WUPD, BK_DIV = 0, 1, 2, 3
 
 
 class OptionsT(ctypes.Structure):
@@ -62,6 +62,7 @@ EXPORTED = [
     "nmfc_calculate_norm_dev", "nmfc_calculate_maxchange_dev", "nmfc_nmf_mu_release",
     "nmfc_brunet_default_opts", "nmfc_brunet_create", "nmfc_brunet_destroy", "nmfc_brunet_run",
     "nmfc_brunet_set_timing", "nmfc_brunet_kernel_time", "nmfc_build_tuning", "nmfc_build_tuning_brunet",
+    "nmfc_brunet_set_divergence", "nmfc_brunet_divergence", "nmfc_brunet_best", "nmfc_brunet_log_probe",
 ]
 
 _LIB = None
@@ -172,6 +173,14 @@ def lib() -> ctypes.CDLL:
     L.nmfc_brunet_set_timing.restype = None
     L.nmfc_brunet_kernel_time.argtypes = [ctypes.c_void_p, c_int, _dp, _dp]
     L.nmfc_brunet_kernel_time.restype = ctypes.c_longlong
+    L.nmfc_brunet_set_divergence.argtypes = [ctypes.c_void_p, c_int]
+    L.nmfc_brunet_set_divergence.restype = None
+    L.nmfc_brunet_divergence.argtypes = [ctypes.c_void_p, _dp]
+    L.nmfc_brunet_divergence.restype = c_int
+    L.nmfc_brunet_best.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp]
+    L.nmfc_brunet_best.restype = c_int
+    L.nmfc_brunet_log_probe.argtypes = [ctypes.c_void_p, _dp, c_int, _dp]
+    L.nmfc_brunet_log_probe.restype = c_int
     _LIB = L
     return L
 

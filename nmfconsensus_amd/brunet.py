@@ -10,7 +10,8 @@ test_nmf.r:29) but does not ship.  Names and argument meaning follow that script
 Every compute step calls nmfconsensus_amd/libnmf.so (nmfc_brunet_*, HIP gfx950); there is no CPU
 fallback.  Restart i (1-based) of every k runs set.seed(rseed + i) then W <- runif(m k), H <- runif(k n)
 (R's Mersenne-Twister, bit-exact).  NMF.div's error.v trace (a per-iteration log-sum over A, not used
-by the consensus) is not computed.  Parity vs the reference is unpinned (the script is not in the
+by the consensus) is not computed; its value for the factors a run returns is (want_divergence, want_best: one device
+pass per k batch, and only each k's best restart's factors leave the GPU).  Parity vs the reference is unpinned (the script is not in the
 reference); the oracle is oracle/brunet_oracle.c.
 """
 from __future__ import annotations
@@ -78,11 +79,48 @@ class BrunetEngine:
         cnt = self.L.nmfc_brunet_kernel_time(self.h, kid, ctypes.byref(ms), ctypes.byref(fl))
         return cnt, ms.value, fl.value
 
+    def set_divergence(self, on: bool):
+        """Later runs also compute every job's KL divergence (nmfc_brunet_set_divergence)."""
+        self.L.nmfc_brunet_set_divergence(self.h, 1 if on else 0)
+        self._divergence = bool(on)
+
+    def divergence(self, nk: int, B: int) -> np.ndarray:
+        """(nk, B) divergences of the last run's shard, which must have had them enabled (nmfc_brunet_divergence)."""
+        out = np.zeros((nk, B), dtype=np.float64)
+        if self.L.nmfc_brunet_divergence(self.h, out.ctypes.data_as(_dp)) != nk * B:
+            raise RuntimeError(f"nmfc_brunet_divergence failed: {_lib.last_error()}")
+        return out
+
+    def best(self, ks):
+        """(best_restart, best_divergence, best_W, best_H) per k of the last run's shard (nmfc_brunet_best): the restart
+        with the smallest divergence, the lowest on ties, and its factors -- the only ones copied off the device."""
+        m, n, nk = self.m, self.n, len(ks)
+        br = np.zeros(nk, dtype=np.int32)
+        bd = np.zeros(nk, dtype=np.float64)
+        wflat = np.zeros(m * sum(ks), dtype=np.float64)
+        hflat = np.zeros(n * sum(ks), dtype=np.float64)
+        if self.L.nmfc_brunet_best(self.h, br.ctypes.data_as(_ip), bd.ctypes.data_as(_dp), wflat.ctypes.data_as(_dp),
+                                   hflat.ctypes.data_as(_dp)) != nk:
+            raise RuntimeError(f"nmfc_brunet_best failed: {_lib.last_error()}")
+        Ws, Hs = [], []
+        wo = ho = 0
+        for k in ks:
+            Ws.append(wflat[wo:wo + m * k].reshape((m, k), order="F"))
+            Hs.append(hflat[ho:ho + k * n].reshape((k, n), order="F"))
+            wo += m * k
+            ho += k * n
+        return [int(x) for x in br], [float(x) for x in bd], Ws, Hs
+
     def run(self, ks, R: int, *, maxiter: int = 2000, seed: int = 123456789, stopconv: int = 40, stopfreq: int = 10,
             restart_begin: int = 0, restart_end: int = -1, W_init=None, H_init=None, want_factors: bool = False,
             want_counts: bool = True, counts_device_ptr: int | None = None, verbose: bool = False,
-            lanes: int = 0) -> SweepResult:
-        """Jobs in nmfconsensus order (for k in ks: for i in restart shard); per-job arrays follow it."""
+            lanes: int = 0, want_divergence: bool = False, want_best: bool = False) -> SweepResult:
+        """Jobs in nmfconsensus order (for k in ks: for i in restart shard); per-job arrays follow it.
+
+        want_divergence: SweepResult.divergence, (nk, restarts of the shard), every job's KL divergence (NMF.div's
+        error.v figure) on its final factors, from one device pass per k batch; want_best (implies want_divergence):
+        best_restart, best_divergence, best_W, best_H, per k the restart with the smallest divergence and its factors,
+        the only ones that leave the device.  Both hold for this call only; set_divergence() is restored after it."""
         ks = [int(k) for k in ks]
         nk = len(ks)
         rb = max(0, restart_begin)
@@ -128,11 +166,21 @@ class BrunetEngine:
             if wi.size != sum(m * k for k in jk) or hi.size != sum(k * n for k in jk):
                 raise ValueError("W_init/H_init sizes do not match the job shard")
         ks_arr = np.array(ks, dtype=np.int32)
-        rc = self.L.nmfc_brunet_run(self.h, ks_arr.ctypes.data_as(_ip), nk, R, ctypes.byref(o),
-                                    wi.ctypes.data_as(_dp) if wi is not None else None,
-                                    hi.ctypes.data_as(_dp) if hi is not None else None, ctypes.byref(res))
+        prev = getattr(self, "_divergence", False)
+        want_divergence = want_divergence or want_best or prev
+        if want_divergence != prev:
+            self.set_divergence(want_divergence)
+        try:
+            rc = self.L.nmfc_brunet_run(self.h, ks_arr.ctypes.data_as(_ip), nk, R, ctypes.byref(o),
+                                        wi.ctypes.data_as(_dp) if wi is not None else None,
+                                        hi.ctypes.data_as(_dp) if hi is not None else None, ctypes.byref(res))
+        finally:
+            if want_divergence != prev:
+                self.set_divergence(prev)
         if rc != 0:
             raise RuntimeError(f"nmfc_brunet_run failed: {_lib.last_error()}")
+        div = self.divergence(nk, B) if want_divergence else None
+        best = self.best(ks) if want_best else (None, None, None, None)
         Ws = Hs = None
         if want_factors:
             Ws, Hs = [], []
@@ -145,26 +193,33 @@ class BrunetEngine:
         return SweepResult(ks=ks, R=R, n=n, counts=counts, consensus=consensus, labels=labels, iters=iters,
                            stopped_early=early, W=Ws, H=Hs, seconds_total=res.seconds_total,
                            seconds_iterate=res.seconds_iterate, restart_iterations=res.restart_iterations,
-                           max_iter_run=res.max_iter_run, job_begin=rb, job_end=re)
+                           max_iter_run=res.max_iter_run, job_begin=rb, job_end=re, divergence=div,
+                           best_restart=best[0], best_divergence=best[1], best_W=best[2], best_H=best[3])
 
 
 def NMF_div(V, k: int, maxniter: int = 2000, seed: int = 123456, stopconv: int = 40, stopfreq: int = 10,
-            device: int = -1) -> dict:
-    """NMF.div: one Brunet KL-divergence restart from set.seed(seed).  Returns dict(W, H, t)."""
+            device: int = -1, want_divergence: bool = False, want_best: bool = False) -> dict:
+    """NMF.div: one Brunet KL-divergence restart from set.seed(seed).  Returns dict(W, H, t); with want_divergence
+    (or want_best, which for one restart asks the same) also 'divergence', error.v of the returned factors."""
     with BrunetEngine(V, device) as eng:
         # restart i = 1 of a one-restart sweep runs set.seed(rseed + 1)
         r = eng.run([k], 1, maxiter=maxniter, seed=seed - 1, stopconv=stopconv, stopfreq=stopfreq,
-                    want_factors=True, want_counts=False)
-    return {"W": r.W[0], "H": r.H[0], "t": int(r.iters[0])}
+                    want_factors=True, want_counts=False, want_divergence=want_divergence or want_best)
+    out = {"W": r.W[0], "H": r.H[0], "t": int(r.iters[0])}
+    if r.divergence is not None:
+        out["divergence"] = float(r.divergence[0, 0])
+    return out
 
 
 def nmfconsensus(input_ds, k_init: int, k_final: int, num_clusterings: int, maxniter: int,
                  error_function: str = "divergence", rseed: int = 123456789, directory: str | None = None,
-                 stopconv: int = 40, stopfreq: int = 10, doc_string: str = "", device: int = -1) -> dict:
+                 stopconv: int = 40, stopfreq: int = 10, doc_string: str = "", device: int = -1,
+                 want_divergence: bool = False, want_best: bool = False) -> dict:
     """The BROAD consensus sweep: for k in k_init..k_final, num_clusterings Brunet restarts, membership
     = argmax of each H column, connectivity summed and divided by num_clusterings, then the cophenetic
     correlation, ordering and cutree membership (computeConsensusAndSaveFiles).  input_ds is an m x n
-    array or a .gct path."""
+    array or a .gct path.  want_divergence adds 'divergence', (nk, num_clusterings); want_best adds that and 'best',
+    {k: dict(restart=<0-based>, divergence=, W=<m x k>, H=<k x n>)}: the best metagenes per k."""
     if error_function != "divergence":
         raise NotImplementedError("only error_function='divergence' (Brunet KL MU) is implemented")
     if k_init < 2 or k_final < k_init:
@@ -176,8 +231,14 @@ def nmfconsensus(input_ds, k_init: int, k_final: int, num_clusterings: int, maxn
         A = input_ds
     ks = list(range(k_init, k_final + 1))
     with BrunetEngine(A, device) as eng:
-        sw = eng.run(ks, num_clusterings, maxiter=maxniter, seed=rseed, stopconv=stopconv, stopfreq=stopfreq)
+        sw = eng.run(ks, num_clusterings, maxiter=maxniter, seed=rseed, stopconv=stopconv, stopfreq=stopfreq,
+                     want_divergence=want_divergence, want_best=want_best)
     result = {str(k): sw.consensus[i] for i, k in enumerate(ks)}
     out = computeConsensusAndSaveFiles(result, save_dir=directory, doc_string=doc_string)
     out["sweep"] = sw
+    if want_divergence or want_best:
+        out["divergence"] = sw.divergence
+    if want_best:
+        out["best"] = {k: dict(restart=sw.best_restart[i], divergence=sw.best_divergence[i], W=sw.best_W[i],
+                               H=sw.best_H[i]) for i, k in enumerate(ks)}
     return out

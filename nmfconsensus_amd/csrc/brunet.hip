@@ -640,6 +640,131 @@ __global__ void k_br_layout(const double* __restrict__ A, int m, int n, long m_p
   if (!(v >= 0.0 && v <= 0x1p64)) *bad = 1;   // NaN fails both tests
 }
 
+// ---- KL divergence of a batch's final factors (nmfc_brunet_set_divergence) -------------------------------
+// D_b = sum_{i,j} (a log((a + eps) / (p + eps)) - a + p) / (m n), p = sum_q W_b[i][q] H_b[j][q]: NMF.div's error.v figure
+// (oracle/brunet_oracle.c) on the factors the run returns.  A tile is DIV_GT genes (one per lane) by DIV_ST samples
+// (DIV_WJ per wave): a thread keeps its DIV_WJ values of A in registers and walks all B restarts of the batch over them,
+// so A is read once per batch.  Per restart it holds its row of W (K contiguous doubles) in registers; the restart's H
+// columns are wave-uniform.  The tiling and every summation order are functions of (m, n) alone.
+constexpr int DIV_GT = 64;
+constexpr int DIV_WJ = 8;
+constexpr int DIV_ST = (BT / 64) * DIV_WJ;
+static_assert(BT / 64 == 4, "k_br_div adds four wave sums");
+constexpr int DIV_JG = 16;   // restarts between two workgroup barriers (the LDS rows of the wave sums)
+// VALU instructions of the device log() as hipcc compiles it for gfx950 (counted in the ISA listing: 83 from
+// v_frexp_mant_f64 to the last special-case select, its literal moves left out; one sample's stretch of k_br_div<2>
+// holds 102 = 83 + 2 FMAs + 17 for the two eps adds, the IEEE division, a log r - a + p, the select and the running
+// sum).  Kernel id 3 of nmfc_brunet_kernel_time is priced at 2k + 6 + BR_LOG_OPS lane-operations per element.
+constexpr int BR_LOG_OPS = 83;
+
+// one element's term from the oracle's expression, one rounding per operation, the quotient an IEEE division; a = 0
+// gives exactly p
+__device__ __forceinline__ double div_term(double a, double p) {
+  const double lg = log(__ddiv_rn(__dadd_rn(a, EPS), __dadd_rn(p, EPS)));
+  return __dadd_rn(__dsub_rn(__dmul_rn(a, lg), a), p);
+}
+
+// grid x: tiles, gene tile major with nst sample tiles each.  part[b][tile] = the tile's sum for restart b: a thread adds
+// its samples in order, the wave by the xor butterfly (every lane ends with the same bits), the four waves in wave order.
+// Needs n >= DIV_WJ (narrower matrices: k_br_div_narrow).  A wave whose DIV_WJ samples would pass n starts at
+// n - DIV_WJ instead and drops the samples below its own first one by a select, so its reads sit at constant offsets
+// inside Acm and the restart's own H.  Rows >= m read row m - 1 of W and are dropped by the same select.
+template <int K>
+__global__ __launch_bounds__(BT) void k_br_div(const double* __restrict__ Acm, long m_pad, int m, int n, int nst, int B,
+                                               const double* __restrict__ W, long wstride,
+                                               const double* __restrict__ H, long hstride, double* __restrict__ part,
+                                               int ntiles) {
+  __shared__ double red[DIV_JG][BT / 64];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int tile = blockIdx.x, gt = tile / nst, stl = tile - gt * nst;
+  const int i = gt * DIV_GT + lane;            // < m_pad (a multiple of BT): every Acm read stays inside its column
+  const int il = i < m ? i : m - 1;
+  const int j0 = stl * DIV_ST + wave * DIV_WJ; // the wave's first sample
+  const int jb = min(j0, n - DIV_WJ);          // the first sample read: 0 <= jb, jb + DIV_WJ <= n
+  const int skip = i < m ? j0 - jb : DIV_WJ;   // samples u < skip are not this thread's: all of them when j0 >= n
+  double av[DIV_WJ];
+#pragma unroll
+  for (int u = 0; u < DIV_WJ; ++u) av[u] = Acm[(long)(jb + u) * m_pad + i];
+  const double* wr = W + (long)il * K;   // this thread's row of W and the wave's first column of H, restart 0
+  const double* hj = H + (long)jb * K;
+  double* po = part + (long)threadIdx.x * ntiles + tile;   // thread t stores restart t's sum of each round of DIV_JG
+#pragma unroll 1
+  for (int b = 0; b < B; ++b, wr += wstride, hj += hstride) {
+    double w[K];
+#pragma unroll
+    for (int q = 0; q < K; ++q) w[q] = wr[q];
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < DIV_WJ; ++u) {
+      double p = 0.0;
+#pragma unroll
+      for (int q = 0; q < K; ++q) {
+        p = fma(w[q], hj[u * K + q], p);
+        // a long H column is consumed four entries at a time in the schedule (two or one where the column is no
+        // multiple of 32 bytes): the counts at which no scalar register is spilled, as the barrier per sample below
+        constexpr int QM = K == 15 ? 0 : (K & 3) ? 1 : 3;
+        if (K >= 12 && (q & QM) == QM) __builtin_amdgcn_sched_barrier(0);
+      }
+      const double t = div_term(av[u], p);
+      s = __dadd_rn(s, u >= skip ? t : 0.0);
+      // one sample at a time in the schedule: with several H columns hoisted the scalar registers spill
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const int r = b & (DIV_JG - 1);
+    if (lane == 0) red[r][wave] = s;
+    if (r == DIV_JG - 1 || b == B - 1) {   // the wave sums of the last r + 1 restarts, in wave order
+      __syncthreads();
+      if ((int)threadIdx.x <= r) {
+        const double* p = red[threadIdx.x];
+        *po = ((p[0] + p[1]) + p[2]) + p[3];
+      }
+      __syncthreads();
+      po += (long)DIV_JG * ntiles;
+    }
+  }
+}
+
+// n < DIV_WJ (one sample tile, all of it wave 0's): the same sums in the same order by rolled loops, any K.  One wave
+// per gene tile and restart; part[b][tile] as k_br_div writes it (the other three wave sums are 0).
+__global__ __launch_bounds__(64) void k_br_div_narrow(const double* __restrict__ Acm, long m_pad, int m, int n, int K,
+                                                      const double* __restrict__ W, long wstride,
+                                                      const double* __restrict__ H, long hstride,
+                                                      double* __restrict__ part, int ntiles) {
+  const int tile = blockIdx.x, b = blockIdx.y;
+  const int i = tile * DIV_GT + threadIdx.x, il = i < m ? i : m - 1;
+  const double* wr = W + (long)b * wstride + (long)il * K;
+  const double* hb = H + (long)b * hstride;
+  double s = 0.0;
+  for (int u = 0; u < n; ++u) {
+    double p = 0.0;
+    for (int q = 0; q < K; ++q) p = fma(wr[q], hb[u * K + q], p);
+    const double t = div_term(Acm[(long)u * m_pad + i], p);
+    s = __dadd_rn(s, i < m ? t : 0.0);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if (threadIdx.x == 0) part[(long)b * ntiles + tile] = ((s + 0.0) + 0.0) + 0.0;
+}
+
+// div[b] = (restart b's ntiles partials: lane l adds tiles l, l + 64, ... in order, then the butterfly) / (m n)
+__global__ __launch_bounds__(64) void k_br_div_sum(const double* __restrict__ part, int ntiles, double mn,
+                                                   double* __restrict__ div) {
+  const double* p = part + (long)blockIdx.x * ntiles;
+  double s = 0.0;
+  for (int t = threadIdx.x; t < ntiles; t += 64) s += p[t];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if (threadIdx.x == 0) div[blockIdx.x] = s / mn;
+}
+
+// y[i] = log(x[i]) by the device log that k_br_div calls (nmfc_brunet_log_probe: the tests measure it against logl)
+__global__ void k_br_log(const double* __restrict__ x, int len, double* __restrict__ y) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < len) y[i] = log(x[i]);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -650,12 +775,14 @@ __global__ void k_br_layout(const double* __restrict__ A, int m, int n, long m_p
 namespace {
 
 constexpr int BR_LANES = 4;   // = the HW queues HIP gives a process by default (GPU_MAX_HW_QUEUES)
-enum { BK_HNUM = 0, BK_HUPD = 1, BK_WUPD = 2 };
+enum { BK_HNUM = 0, BK_HUPD = 1, BK_WUPD = 2, BK_DIV = 3, BK_N = 4 };
 
 struct BrLane {
   hipStream_t st = nullptr;
   Buf W, H, Gp, RS, memb, nochange, stop_iter, act, seeds, labels;
+  Buf part, div;                 // divergence pass: per (restart, tile) partials, per restart D (only when enabled)
   PinBuf h_si, h_act, h_seeds;   // pinned host mirrors of stop_iter, act, seeds
+  PinBuf h_div;                  // ... and of div
   bool timing = false;
   struct Pending {
     int kid;
@@ -663,15 +790,16 @@ struct BrLane {
   };
   std::vector<Pending> pending;
   std::vector<hipEvent_t> pool;
-  double kms[3] = {0, 0, 0};
-  long long kcount[3] = {0, 0, 0};
-  double kfl_sum[3] = {0, 0, 0};
+  double kms[BK_N] = {0, 0, 0, 0};
+  long long kcount[BK_N] = {0, 0, 0, 0};
+  double kfl_sum[BK_N] = {0, 0, 0, 0};
   void release() {
-    Buf* bufs[] = {&W, &H, &Gp, &RS, &memb, &nochange, &stop_iter, &act, &seeds, &labels};
+    Buf* bufs[] = {&W, &H, &Gp, &RS, &memb, &nochange, &stop_iter, &act, &seeds, &labels, &part, &div};
     for (Buf* b : bufs) b->release();
     h_si.release();
     h_act.release();
     h_seeds.release();
+    h_div.release();
     for (auto v : pool) (void)hipEventDestroy(v);
     pool.clear();
     if (st) (void)hipStreamDestroy(st);
@@ -732,9 +860,16 @@ struct nmfc_brunet {
   Buf Acm, Arm, counts_tmp, cons_tmp;
   BrLane lanes[BR_LANES];
   bool timing = false;
-  double kms[3] = {0, 0, 0};
-  long long kcount[3] = {0, 0, 0};
-  double kfl_sum[3] = {0, 0, 0};
+  double kms[BK_N] = {0, 0, 0, 0};
+  long long kcount[BK_N] = {0, 0, 0, 0};
+  double kfl_sum[BK_N] = {0, 0, 0, 0};
+  // nmfc_brunet_set_divergence: the last run's D per job and, per k index, the best restart and its factors (device,
+  // in the lane layouts W [gene][K], H [sample][K]); a lane writes only the entries of its own k
+  bool divergence = false, div_valid = false;
+  int div_B = 0, div_rb = 0;
+  std::vector<int> div_ks, best_slot;
+  std::vector<double> div_vals;
+  std::vector<Buf> bestW, bestH;
 };
 
 namespace {
@@ -831,6 +966,54 @@ struct KJob {
   long woff, hoff;   // offsets of this k's jobs in the W / H outputs
 };
 
+// D of the B restarts whose final factors lie in L->W / L->H (one pass: k_br_div + k_br_div_sum), the first argmin on
+// the host, and that restart's factors copied to the k's own device buffer before the lane reuses W and H.
+int br_divergence(nmfc_brunet* e, BrLane* L, const KJob& kj, int B) {
+  const int m = e->m, n = e->n, K = kj.K;
+  hipStream_t st = L->st;
+  const int nst = (n + DIV_ST - 1) / DIV_ST, ntiles = (m + DIV_GT - 1) / DIV_GT * nst;
+  const size_t wbytes = sizeof(double) * (size_t)m * K, hbytes = sizeof(double) * (size_t)n * K;
+  if (L->part.ensure(sizeof(double) * (size_t)B * ntiles) || L->div.ensure(sizeof(double) * B) ||
+      L->h_div.ensure(sizeof(double) * B) || e->bestW[kj.ki].ensure(wbytes) || e->bestH[kj.ki].ensure(hbytes))
+    return -1;
+  {
+    BTimed tl(L, BK_DIV, (2.0 * K + 6 + BR_LOG_OPS) * m * n * B);
+    if (n < DIV_WJ)
+      hipLaunchKernelGGL(k_br_div_narrow, dim3(ntiles, B), dim3(64), 0, st, e->Acm.as<double>(), e->m_pad, m, n, K,
+                         L->W.as<double>(), (long)m * K, L->H.as<double>(), (long)n * K, L->part.as<double>(), ntiles);
+    else switch (K) {
+#define BR_DIV_CASE(KK)                                                                                             \
+  case KK:                                                                                                           \
+    hipLaunchKernelGGL((k_br_div<KK>), dim3(ntiles), dim3(BT), 0, st, e->Acm.as<double>(), e->m_pad, m, n, nst, B,   \
+                       L->W.as<double>(), (long)m * KK, L->H.as<double>(), (long)n * KK, L->part.as<double>(), ntiles); \
+    break;
+      BR_DIV_CASE(2) BR_DIV_CASE(3) BR_DIV_CASE(4) BR_DIV_CASE(5) BR_DIV_CASE(6) BR_DIV_CASE(7) BR_DIV_CASE(8)
+      BR_DIV_CASE(9) BR_DIV_CASE(10) BR_DIV_CASE(11) BR_DIV_CASE(12) BR_DIV_CASE(13) BR_DIV_CASE(14) BR_DIV_CASE(15)
+      BR_DIV_CASE(16)
+#undef BR_DIV_CASE
+      default:
+        br_err("nmfc_brunet_run: k=%d unsupported", K);
+        return -1;
+    }
+    hipLaunchKernelGGL(k_br_div_sum, dim3(B), dim3(64), 0, st, L->part.as<double>(), ntiles, (double)m * n,
+                       L->div.as<double>());
+  }
+  BCHECK(hipGetLastError());
+  double* d = L->h_div.as<double>();
+  BCHECK(hipMemcpyAsync(d, L->div.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+  BCHECK(hipStreamSynchronize(st));
+  if (L->timing) br_drain(L);
+  int best = 0;
+  for (int b = 0; b < B; ++b) {
+    e->div_vals[(size_t)kj.ki * B + b] = d[b];
+    if (d[b] < d[best]) best = b;   // the lowest restart on ties
+  }
+  e->best_slot[kj.ki] = best;
+  BCHECK(hipMemcpyAsync(e->bestW[kj.ki].p, L->W.as<double>() + (size_t)best * m * K, wbytes, hipMemcpyDeviceToDevice, st));
+  BCHECK(hipMemcpyAsync(e->bestH[kj.ki].p, L->H.as<double>() + (size_t)best * n * K, hbytes, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 int br_run_k(nmfc_brunet* e, BrLane* L, const KJob& kj, int B, int R, const nmfc_brunet_opts& o, const double* W_init,
              const double* H_init, int32_t* dcounts, nmfc_result* out, long long* tot_iters, int* max_it) {
   const int m = e->m, n = e->n, K = kj.K, ki = kj.ki;
@@ -876,6 +1059,7 @@ int br_run_k(nmfc_brunet* e, BrLane* L, const KJob& kj, int B, int R, const nmfc
   BCHECK(hipStreamSynchronize(st));   // seeds / hw host buffers
   std::vector<int> iters, stopped;
   if (br_dispatch(e, L, K, B, o, iters, stopped)) return -1;
+  if (e->divergence && br_divergence(e, L, kj, B)) return -1;
   hipLaunchKernelGGL(k_br_labels, dim3((n + BT - 1) / BT, B), dim3(BT), 0, st, L->H.as<double>(), hstride, K, n,
                      L->labels.as<int32_t>());
   BCHECK(hipGetLastError());
@@ -1003,6 +1187,8 @@ void nmfc_brunet_destroy(nmfc_brunet* e) {
   }
   Buf* bufs[] = {&e->Acm, &e->Arm, &e->counts_tmp, &e->cons_tmp};
   for (Buf* b : bufs) b->release();
+  for (Buf& b : e->bestW) b.release();
+  for (Buf& b : e->bestH) b.release();
   if (e->st) (void)hipStreamDestroy(e->st);
   delete e;
 }
@@ -1012,14 +1198,97 @@ void nmfc_brunet_set_timing(nmfc_brunet* e, int enable) {
 }
 
 long long nmfc_brunet_kernel_time(nmfc_brunet* e, int kid, double* ms_out, double* flops_per_launch) {
-  if (!e || kid < 0 || kid > 2) return -1;
+  if (!e || kid < 0 || kid >= BK_N) return -1;
   if (ms_out) *ms_out = e->kms[kid];
   if (flops_per_launch) *flops_per_launch = e->kcount[kid] ? e->kfl_sum[kid] / e->kcount[kid] : 0.0;
   return e->kcount[kid];
 }
 
+void nmfc_brunet_set_divergence(nmfc_brunet* e, int enable) {
+  if (e) e->divergence = enable != 0;
+}
+
+namespace {
+int div_ready(const nmfc_brunet* e, const char* who) {
+  if (!e) {
+    br_err("%s: NULL engine", who);
+    return -1;
+  }
+  if (!e->div_valid) {
+    br_err("%s: the last run on this engine had the divergence disabled (nmfc_brunet_set_divergence) or failed", who);
+    return -1;
+  }
+  return 0;
+}
+}  // namespace
+
+int nmfc_brunet_divergence(nmfc_brunet* e, double* div_out) {
+  if (div_ready(e, "nmfc_brunet_divergence")) return -1;
+  if (!div_out) {
+    br_err("nmfc_brunet_divergence: NULL output");
+    return -1;
+  }
+  memcpy(div_out, e->div_vals.data(), sizeof(double) * e->div_vals.size());
+  return (int)e->div_vals.size();
+}
+
+int nmfc_brunet_log_probe(nmfc_brunet* e, const double* x, int count, double* y) {
+  if (!e || !x || !y || count <= 0) {
+    br_err("nmfc_brunet_log_probe: bad arguments");
+    return -1;
+  }
+  BCHECK(hipSetDevice(e->dev));
+  Buf dx, dy;
+  if (dx.ensure(sizeof(double) * count) || dy.ensure(sizeof(double) * count)) {
+    dx.release();
+    return -1;
+  }
+  hipError_t err = hipMemcpyAsync(dx.p, x, sizeof(double) * count, hipMemcpyHostToDevice, e->st);
+  if (err == hipSuccess) {
+    hipLaunchKernelGGL(k_br_log, dim3((count + BT - 1) / BT), dim3(BT), 0, e->st, dx.as<double>(), count, dy.as<double>());
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipMemcpyAsync(y, dy.p, sizeof(double) * count, hipMemcpyDeviceToHost, e->st);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->st);
+  dx.release();
+  dy.release();
+  if (err != hipSuccess) {
+    br_err("nmfc_brunet_log_probe: %s", hipGetErrorString(err));
+    return -1;
+  }
+  return 0;
+}
+
+int nmfc_brunet_best(nmfc_brunet* e, int32_t* best_restart_out, double* best_div_out, double* W_out, double* H_out) {
+  if (div_ready(e, "nmfc_brunet_best")) return -1;
+  const int m = e->m, n = e->n, nk = (int)e->div_ks.size();
+  BCHECK(hipSetDevice(e->dev));
+  std::vector<double> tmp;
+  long woff = 0, hoff = 0;
+  for (int ki = 0; ki < nk; ++ki) {
+    const int K = e->div_ks[ki], b = e->best_slot[ki];
+    if (best_restart_out) best_restart_out[ki] = e->div_rb + b;
+    if (best_div_out) best_div_out[ki] = e->div_vals[(size_t)ki * e->div_B + b];
+    if (W_out) {   // the lane layout [gene][K] to m x K column-major
+      tmp.resize((size_t)m * K);
+      BCHECK(hipMemcpyAsync(tmp.data(), e->bestW[ki].p, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, e->st));
+      BCHECK(hipStreamSynchronize(e->st));
+      for (int c = 0; c < K; ++c)
+        for (int i = 0; i < m; ++i) W_out[woff + (long)c * m + i] = tmp[(size_t)i * K + c];
+    }
+    if (H_out) {
+      BCHECK(hipMemcpyAsync(H_out + hoff, e->bestH[ki].p, sizeof(double) * (size_t)n * K, hipMemcpyDeviceToHost, e->st));
+      BCHECK(hipStreamSynchronize(e->st));
+    }
+    woff += (long)m * K;
+    hoff += (long)n * K;
+  }
+  return nk;
+}
+
 int nmfc_brunet_run(nmfc_brunet* e, const int* ks, int nk, int R, const nmfc_brunet_opts* opts_in,
                     const double* W_init, const double* H_init, nmfc_result* out) {
+  if (e) e->div_valid = false;   // until this run has filled them
   if (!e || !ks || nk <= 0 || R <= 0) {
     br_err("nmfc_brunet_run: bad arguments");
     return -1;
@@ -1070,12 +1339,20 @@ int nmfc_brunet_run(nmfc_brunet* e, const int* ks, int nk, int R, const nmfc_bru
   std::vector<KJob> order(jobs);
   std::stable_sort(order.begin(), order.end(), [](const KJob& a, const KJob& b) { return a.K > b.K; });
   const int nl = std::min(o.lanes > 0 ? std::min(o.lanes, BR_LANES) : e->nlanes, nk);
+  if (e->divergence) {
+    e->div_ks.assign(ks, ks + nk);
+    e->div_B = B;
+    e->div_rb = rb;
+    e->div_vals.assign((size_t)nk * B, 0.0);
+    e->best_slot.assign(nk, 0);
+    if ((int)e->bestW.size() < nk) e->bestW.resize(nk), e->bestH.resize(nk);
+  }
   std::vector<long long> lane_iters(nl, 0);
   std::vector<int> lane_max(nl, 0);
   for (int l = 0; l < nl; ++l) {
     BrLane& L = e->lanes[l];
     L.timing = e->timing;
-    for (int q = 0; q < 3; ++q) L.kms[q] = 0, L.kcount[q] = 0, L.kfl_sum[q] = 0;
+    for (int q = 0; q < BK_N; ++q) L.kms[q] = 0, L.kcount[q] = 0, L.kfl_sum[q] = 0;
   }
   // the k batches, largest first, on nl lanes (csrc/lane_pool.hpp; the scheduler alone runs under TSan in the CPU
   // suite): a lane touches only its own BrLane, its lane_iters / lane_max slot and the outputs of its k
@@ -1092,11 +1369,11 @@ int nmfc_brunet_run(nmfc_brunet* e, const int* ks, int nk, int R, const nmfc_bru
   }
   long long tot_iters = 0;
   int max_it = 0;
-  for (int q = 0; q < 3; ++q) e->kms[q] = 0, e->kcount[q] = 0, e->kfl_sum[q] = 0;
+  for (int q = 0; q < BK_N; ++q) e->kms[q] = 0, e->kcount[q] = 0, e->kfl_sum[q] = 0;
   for (int l = 0; l < nl; ++l) {
     tot_iters += lane_iters[l];
     max_it = std::max(max_it, lane_max[l]);
-    for (int q = 0; q < 3; ++q) {
+    for (int q = 0; q < BK_N; ++q) {
       e->kms[q] += e->lanes[l].kms[q];
       e->kcount[q] += e->lanes[l].kcount[q];
       e->kfl_sum[q] += e->lanes[l].kfl_sum[q];
@@ -1115,6 +1392,7 @@ int nmfc_brunet_run(nmfc_brunet* e, const int* ks, int nk, int R, const nmfc_bru
       BCHECK(hipMemcpyAsync(out->counts, dcounts, sizeof(int32_t) * nn * nk, hipMemcpyDeviceToHost, st));
   }
   BCHECK(hipStreamSynchronize(st));
+  e->div_valid = e->divergence;
   auto t1 = std::chrono::steady_clock::now();
   if (out) {
     out->seconds_total = std::chrono::duration<double>(t1 - t0).count();

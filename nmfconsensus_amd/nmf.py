@@ -82,6 +82,12 @@ class SweepResult:
     extras: dict = field(default_factory=dict)
     dnorm: np.ndarray | None = None    # (njobs,) float64: ||A - W_j H_j||_F / sqrt(m n) (want_residuals)
     best: dict | None = None           # {k: dict(job=<global 0-based id>, dnorm=, W=<m x k>, H=<k x n>)} (want_best)
+    # the Brunet engine's per-job KL divergence and best restart per k (BrunetEngine.run want_divergence / want_best)
+    divergence: np.ndarray | None = None       # (nk, restarts of the shard) float64: NMF.div's error.v of the final factors
+    best_restart: list | None = None           # per k: 0-based restart (over all R) with the smallest divergence
+    best_divergence: list | None = None        # per k: its divergence
+    best_W: list | None = None                 # per k: its W (m x k)
+    best_H: list | None = None                 # per k: its H (k x n)
 
 
 class Engine:
