@@ -189,7 +189,10 @@ typedef struct nmfc_brunet nmfc_brunet;
 
 void nmfc_brunet_default_opts(nmfc_brunet_opts* o);
 /* A: m x n column-major, every entry finite, >= 0 and <= 2^64 (else NULL with nmfc_last_error set): the domain in
- * which the kernels' batched reciprocals stay normal (csrc/brunet.hip recip_batch). */
+ * which the kernels' batched reciprocals stay normal (csrc/brunet.hip recip_batch).  Accuracy of the quotients a / (W H)
+ * inside the KL updates (csrc/brunet.hip quot_r): faithful -- one of the two doubles next to the
+ * exact quotient, not always the nearer -- for a = 0 (exactly +0.0) and for a >= 2^-969; for 0 < a < 2^-969, subnormals
+ * included, within max(2^-43 relative, 2^-1074). */
 nmfc_brunet* nmfc_brunet_create(int device, const double* A, int m, int n, int a_on_device);
 void nmfc_brunet_destroy(nmfc_brunet* e);
 int nmfc_brunet_device(const nmfc_brunet* e);   /* as nmfc_engine_device */
@@ -227,6 +230,12 @@ int nmfc_brunet_best(nmfc_brunet* e, int32_t* best_restart_out, double* best_div
 /* Diagnostic: y[i] = log(x[i]) for count host values by the device log the divergence pass calls, so that its error
  * can be measured against a long-double log (the divergence bound of tests/kl_bound.py assumes 2 ulp).  0 or -1. */
 int nmfc_brunet_log_probe(nmfc_brunet* e, const double* x, int count, double* y);
+
+/* Diagnostic: for count = nb * batch host pairs, q[i] = the quotient a[i] / p[i] and r[i] = the refined reciprocal of
+ * p[i] exactly as k_br_hnum / k_br_wupd form them when `batch` (1..5) quotients share one v_rcp_f64: pairs
+ * i = j*batch .. j*batch + batch-1 are one batch, in that order.  r_out may be NULL.  0 or -1. */
+int nmfc_brunet_quot_probe(nmfc_brunet* e, const double* a, const double* p, int count, int batch,
+                           double* q_out, double* r_out);
 
 /* calculateNorm (calculatenorm.c:44-78) and calculateMaxchange (calculatemaxchange.c:42-71) on
  * DEVICE-resident column-major operands (e.g. torch tensors) on the current HIP device: d = a - w h and

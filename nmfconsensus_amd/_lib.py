@@ -63,6 +63,7 @@ EXPORTED = [
     "nmfc_brunet_default_opts", "nmfc_brunet_create", "nmfc_brunet_destroy", "nmfc_brunet_run",
     "nmfc_brunet_set_timing", "nmfc_brunet_kernel_time", "nmfc_build_tuning", "nmfc_build_tuning_brunet",
     "nmfc_brunet_set_divergence", "nmfc_brunet_divergence", "nmfc_brunet_best", "nmfc_brunet_log_probe",
+    "nmfc_brunet_quot_probe",
 ]
 
 _LIB = None
@@ -181,6 +182,8 @@ def lib() -> ctypes.CDLL:
     L.nmfc_brunet_best.restype = c_int
     L.nmfc_brunet_log_probe.argtypes = [ctypes.c_void_p, _dp, c_int, _dp]
     L.nmfc_brunet_log_probe.restype = c_int
+    L.nmfc_brunet_quot_probe.argtypes = [ctypes.c_void_p, _dp, _dp, c_int, c_int, _dp, _dp]
+    L.nmfc_brunet_quot_probe.restype = c_int
     _LIB = L
     return L
 

@@ -111,6 +111,19 @@ class BrunetEngine:
             ho += k * n
         return [int(x) for x in br], [float(x) for x in bd], Ws, Hs
 
+    def quot_probe(self, a, p, batch: int):
+        """(q, r): the quotients a / p and the refined reciprocals of p as the KL kernels form them when `batch` (1..5)
+        consecutive pairs share one hardware reciprocal (nmfc_brunet_quot_probe; a test diagnostic)."""
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        p = np.ascontiguousarray(p, dtype=np.float64).ravel()
+        if a.size != p.size:
+            raise ValueError("a and p must have the same size")
+        q, r = np.empty_like(a), np.empty_like(a)
+        if self.L.nmfc_brunet_quot_probe(self.h, a.ctypes.data_as(_dp), p.ctypes.data_as(_dp), a.size, int(batch),
+                                         q.ctypes.data_as(_dp), r.ctypes.data_as(_dp)) != 0:
+            raise RuntimeError(f"nmfc_brunet_quot_probe failed: {_lib.last_error()}")
+        return q, r
+
     def run(self, ks, R: int, *, maxiter: int = 2000, seed: int = 123456789, stopconv: int = 40, stopfreq: int = 10,
             restart_begin: int = 0, restart_end: int = -1, W_init=None, H_init=None, want_factors: bool = False,
             want_counts: bool = True, counts_device_ptr: int | None = None, verbose: bool = False,

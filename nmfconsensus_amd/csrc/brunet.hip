@@ -126,11 +126,19 @@ struct PinBuf {
 // q = a / p from a refined reciprocal r of p: q = a r and one residual correction (Markstein's final step), i.e. the
 // compiler's IEEE sequence without its operand-scaling steps (div_scale / div_fmas / div_fixup), which only matter
 // near the exponent limits, and without its second Newton step.  r comes from v_rcp_f64 (good to 2^-24.4 on gfx950)
-// and one Newton step (~2^-48.8), so the corrected quotient's error is ~2^-97 relative before its rounding: the result
-// is FAITHFUL, and it matched the correctly rounded a / p on every one of 3.2e9 random probe pairs (tools/quot_probe.hip,
-// a, p over 2^-60..2^10) -- but it is not proven correctly rounded: a quotient can sit closer to a rounding midpoint
-// (down to ~2^-106) than the remaining error, and random pairs almost never hit those cases, so bit parity with an IEEE
-// divide is unpinned for them.  Parity to the IEEE-divide oracle on the tested sweeps: tests/test_gpu_brunet.py.
+// and one Newton step (|1 - p r| <= 2^-48.6 measured on the device over the whole admitted domain, batched or not), so
+// the corrected quotient's error is ~2^-97 relative before its rounding.  The contract (measured
+// by tests/test_gpu_brunet_quot.py through nmfc_brunet_quot_probe, which calls this function):
+//  * a = 0 gives +0.0, and for a >= 2^-969 the result is FAITHFUL: the double just below or just above a / p.  It is
+//    not correctly rounded: of 131 072 constructed quotients 2^-106 from a rounding midpoint, 5.9 % (one quotient per
+//    v_rcp_f64) to 8.1 % (five) come out as the other neighbour.  Random operands get that close with probability
+//    below 2^-43: 0 of 3.2e9 random probe pairs (tools/quot_probe.hip) and 0 of 7e6 at the ends of the domain differ
+//    from IEEE a / p, and iterations and labels equal the IEEE-divide oracle's on the tested sweeps
+//    (tests/test_gpu_brunet.py).
+//  * for 0 < a < 2^-969 the last bit of the exact residual, 2^(e_a - 105), is below 2^-1074: fma(-p, q, a) is rounded
+//    on the subnormal grid (for subnormal a usually to zero) and the result tends to the uncorrected a r, so only
+//    |q - a / p| <= max(2^-43 |a / p|, 2^-1074) is promised (measured: at most 17.3 ulp, and a whole ulp off only for
+//    a < 2^-1021).  Such entries do not occur in expression data; no scaling step is spent on them here.
 // NMFC_BRUNET_IEEEDIV (a build of tools/build_variant.sh) is the exact IEEE option.
 __device__ __forceinline__ double quot_r(double a, double p, double r) {
 #if NMFC_BRUNET_IEEEDIV
@@ -148,7 +156,8 @@ __device__ __forceinline__ double quot_r(double a, double p, double r) {
 // rate on gfx950 (6.9 vs 2.1 ns per wave instruction per SIMD, tools/quot_probe.hip rate mode,
 // profiles/r06/brunet_rcp/), so a batch of N trades N - 1 of them for 3 (N - 1) multiplies.  Each r_i carries the
 // Newton error plus at most 2 N roundings of 2^-53, so the corrected quotient keeps its ~2^-96 error and stays faithful
-// (0 differences from IEEE a / p in 3.2e9 batched probe quotients).  The prefix products must stay normal: with A
+// (0 differences from IEEE a / p in 3.2e9 batched probe quotients; on the device the order of a batch and prefix
+// products down to 2^-1020 change nothing, tests/test_gpu_brunet_quot.py).  The prefix products must stay normal: with A
 // finite, non-negative and at most 2^64 (checked by nmfc_brunet_create) and caller factors in [2^-60, 2^60] (checked by
 // nmfc_brunet_run), every VP of the KL updates lies in [eps^2 / T, T] for T = sum(A) <= 2^100 -- the H update makes the
 // column sums of W H equal those of A (the W update the row sums), and the eps terms floor W and H at eps over the
@@ -765,6 +774,24 @@ __global__ void k_br_log(const double* __restrict__ x, int len, double* __restri
   if (i < len) y[i] = log(x[i]);
 }
 
+// One batch of N quotients per thread by the hot loops' own recip_batch<N> and quot_r (nmfc_brunet_quot_probe: the
+// tests measure them at the ends of the reciprocals' domain).  Thread j handles pairs j N .. j N + N - 1.
+template <int N>
+__global__ void k_br_quot(const double* __restrict__ a, const double* __restrict__ p, int nb, double* __restrict__ q,
+                          double* __restrict__ r) {
+  const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nb) return;
+  double pp[N], rr[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) pp[i] = p[j * N + i];
+  recip_batch<N>(pp, rr);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    q[j * N + i] = quot_r(a[j * N + i], pp[i], rr[i]);
+    r[j * N + i] = rr[i];
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1254,6 +1281,52 @@ int nmfc_brunet_log_probe(nmfc_brunet* e, const double* x, int count, double* y)
   dy.release();
   if (err != hipSuccess) {
     br_err("nmfc_brunet_log_probe: %s", hipGetErrorString(err));
+    return -1;
+  }
+  return 0;
+}
+
+int nmfc_brunet_quot_probe(nmfc_brunet* e, const double* a, const double* p, int count, int batch, double* q_out,
+                           double* r_out) {
+  if (!e || !a || !p || !q_out || count <= 0 || batch < 1 || batch > BR_RCP_MAX || count % batch != 0) {
+    br_err("nmfc_brunet_quot_probe: bad arguments (count=%d must be a positive multiple of batch=%d in 1..%d)", count,
+           batch, BR_RCP_MAX);
+    return -1;
+  }
+  BCHECK(hipSetDevice(e->dev));
+  const size_t bytes = sizeof(double) * (size_t)count;
+  const int nb = count / batch;
+  Buf da, dp, dq, dr;
+  hipError_t err = hipSuccess;
+  const bool ok = !da.ensure(bytes) && !dp.ensure(bytes) && !dq.ensure(bytes) && !dr.ensure(bytes);
+  if (ok) {
+    err = hipMemcpyAsync(da.p, a, bytes, hipMemcpyHostToDevice, e->st);
+    if (err == hipSuccess) err = hipMemcpyAsync(dp.p, p, bytes, hipMemcpyHostToDevice, e->st);
+    if (err == hipSuccess) {
+      const dim3 grid((nb + BT - 1) / BT), block(BT);
+      const double *xa = da.as<double>(), *xp = dp.as<double>();
+      double *xq = dq.as<double>(), *xr = dr.as<double>();
+      static_assert(BR_RCP_MAX == 5, "nmfc_brunet_quot_probe: one case per batch size");
+      switch (batch) {
+        case 1: hipLaunchKernelGGL(k_br_quot<1>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+        case 2: hipLaunchKernelGGL(k_br_quot<2>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+        case 3: hipLaunchKernelGGL(k_br_quot<3>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+        case 4: hipLaunchKernelGGL(k_br_quot<4>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+        default: hipLaunchKernelGGL(k_br_quot<5>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+      }
+      err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(q_out, dq.p, bytes, hipMemcpyDeviceToHost, e->st);
+    if (err == hipSuccess && r_out) err = hipMemcpyAsync(r_out, dr.p, bytes, hipMemcpyDeviceToHost, e->st);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->st);
+  }
+  da.release();
+  dp.release();
+  dq.release();
+  dr.release();
+  if (!ok) return -1;
+  if (err != hipSuccess) {
+    br_err("nmfc_brunet_quot_probe: %s", hipGetErrorString(err));
     return -1;
   }
   return 0;

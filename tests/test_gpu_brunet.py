@@ -167,6 +167,33 @@ def test_bad_arguments():
         B[7, 2] = bad
         with pytest.raises(RuntimeError, match="non-negative"):
             BrunetEngine(B)
+    # ... at the bounds themselves: 2^64 is admitted, the next double is not; a subnormal and -0.0 are admitted, and
+    # -0.0 computes what +0.0 computes
+    B = np.ones((10, 4))
+    B[7, 2] = np.nextafter(2.0 ** 64, np.inf)
+    with pytest.raises(RuntimeError, match="non-negative"):
+        BrunetEngine(B)
+    runs = []
+    for zero in (0.0, -0.0):
+        B = np.ones((10, 4))
+        B[7, 2], B[0, 0], B[9, 3], B[4, 1] = 2.0 ** 64, 5e-324, 2.0 ** -1030, zero
+        with BrunetEngine(B) as eng:
+            runs.append(eng.run([2], 1, maxiter=2, seed=3, stopconv=NOSTOP, want_factors=True, want_counts=False))
+    assert np.signbit(B[4, 1]) and np.isfinite(runs[0].W[0]).all() and np.isfinite(runs[0].H[0]).all()
+    assert runs[0].W[0].tobytes() == runs[1].W[0].tobytes() and runs[0].H[0].tobytes() == runs[1].H[0].tobytes()
+    # caller factors: exactly 2^-60 and 2^60 are admitted, their outward neighbours and NaN are not
+    with BrunetEngine(A) as eng:
+        for lo, hi in ((2.0 ** -60, 2.0 ** 60), (2.0 ** 60, 2.0 ** -60)):
+            W0, H0 = np.full((10, 2), 0.5), np.full((2, 4), 0.5)
+            W0[3, 1], H0[1, 2] = lo, hi
+            r = eng.run([2], 1, maxiter=2, stopconv=NOSTOP, W_init=[W0], H_init=[H0], want_factors=True)
+            assert r.iters[0] == 2 and np.isfinite(r.W[0]).all() and np.isfinite(r.H[0]).all()
+        for bad in (np.nextafter(2.0 ** -60, 0.0), np.nextafter(2.0 ** 60, np.inf), np.nan):
+            for side in (0, 1):
+                W0, H0 = np.full((10, 2), 0.5), np.full((2, 4), 0.5)
+                (W0, H0)[side][1, 1] = bad
+                with pytest.raises(RuntimeError, match="caller factors"):
+                    eng.run([2], 1, maxiter=2, W_init=[W0], H_init=[H0])
 
 
 def test_c5_full_size_stop_rule_vs_oracle():

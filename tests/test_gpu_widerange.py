@@ -11,7 +11,8 @@ the references and the conditions on the data on the CPU.
 Labels, counts and consensus of every engine run are checked against numpy on the engine's own H (first maximum under
 ARGMAX, first minimum under R_ORDER, ties included: the all-zero sample column gets label 1).  One case per MU path also
 runs T = 40 against the fp64 oracle: identical zero pattern, relfro < 1e-9.  calculateNorm, the one place with a
-subtraction, is held to its elementwise backward bound.
+subtraction, is held to its elementwise backward bound.  The KL kernels also run at the corners of the domain they admit
+(widerange.CORNER_*: A at 2^64 or 2^-200, caller factors at 2^+-59 alternating inside every restart group).
 
 Every test prints the worst error in u = 2^-53 beside its bound (lines starting "WR|").
 """
@@ -326,3 +327,46 @@ def test_calculate_norm_elementwise(m, n, k):
     assert np.isfinite(d).all() and np.isfinite(v)
     assert ratio <= 1.0
     assert nerr <= nlim
+
+
+# ---- the KL kernels at the corners of the domain they admit ------------------------------------------------------------
+
+@pytest.mark.parametrize("kind,m,n,ks", wr.CORNER_CASES, ids=[f"{c[0]}-{c[1]}x{c[2]}" for c in wr.CORNER_CASES])
+def test_kl_corners(oracle, big_batch, kind, m, n, ks):
+    """A at 2^64, at 2^-200 or spread over 2^-60..2^64, caller factors at 2^+-59 in the four sign combinations,
+    restart i taking combination i % 4: every restart group multiplies VP values about 2^236 apart in one batched
+    reciprocal.  T = 1 and 2: every element within the derived bound of the long-double reference.  T = 40: finite and
+    within 1e-9 of the oracle.  Labels and counts from the run's own H; job 0 alone equals job 0 in the big batch."""
+    from nmfconsensus_amd.brunet import BrunetEngine
+    worst = Worst(f"corner-{kind}")
+    for k in ks:
+        wr.prefetch(kind, m, n, k, range(big_batch))
+    A = wr.case(kind, m, n, ks[0])[0]
+    alone = {}
+    with BrunetEngine(A) as eng:
+        for B in (1, big_batch):
+            jobs = [(k, i) for k in ks for i in range(B)]
+            W0 = [wr.case(kind, m, n, k, i)[1] for k, i in jobs]
+            H0 = [wr.case(kind, m, n, k, i)[2] for k, i in jobs]
+            of_k = [list(range(q * B, (q + 1) * B)) for q in range(len(ks))]
+            for T in (1, 2, wr.CORNER_T):
+                r = eng.run(list(ks), B, maxiter=T, stopconv=NOSTOP, W_init=W0, H_init=H0, want_factors=True)
+                assert np.all(r.iters == T) and not r.stopped_early.any()
+                check_labels(r, of_k, B, n, np.argmax)
+                far = 0.0
+                for j, (k, i) in enumerate(jobs):
+                    if T <= 2:
+                        worst.check(kind, m, n, k, i, T, r.W[j], r.H[j])
+                    else:
+                        assert np.isfinite(r.W[j]).all() and np.isfinite(r.H[j]).all(), (k, i)
+                        Wo, Ho, _ = oracle.brunet(A, W0[j], H0[j], T, NOSTOP)
+                        ew, eh = relfro(r.W[j], Wo), relfro(r.H[j], Ho)
+                        far = max(far, ew, eh)
+                        assert ew < TOL and eh < TOL, (k, i, ew, eh)
+                    if i == 0 and B == 1:
+                        alone[(k, T)] = (r.W[j], r.H[j])
+                    elif i == 0:
+                        assert np.array_equal(alone[(k, T)][0], r.W[j]) and np.array_equal(alone[(k, T)][1], r.H[j]), (k, T)
+                if T > 2:
+                    print(f"WR|corner-{kind}|{m}x{n}|B={B}|T={T}|worst relfro against the oracle {far:.2e}")
+    worst.report()

@@ -172,3 +172,63 @@ def test_constant_sensitivity(m, n, k):
         W, H = mu_fp64(Au, Wu, Hu, 24, eps)
         print(f"constant {name} on uniform {m}x{n} k={k}, T=24: relfro W {relfro(W, Wt):.2e} H {relfro(H, Ht):.2e} "
               f"(the bar is 1e-9)")
+
+
+# ---- the KL kernels at the corners of their domain (widerange.CORNER_*) ------------------------------------------------
+
+CORNER = [(kind, m, n, k) for kind, m, n, ks in wr.CORNER_CASES for k in ks]
+
+
+@pytest.mark.parametrize("kind,m,n,k", CORNER, ids=[f"{c[0]}-{c[1]}x{c[2]}-k{c[3]}" for c in CORNER])
+def test_kl_corner_oracle_in_bound(oracle, kind, m, n, k):
+    """The fp64 oracle passes the componentwise bound at T = 1 and 2 on the four factor-scale combinations, and the
+    inputs sit where nmfc_brunet_create / nmfc_brunet_run admit them."""
+    A = wr.case(kind, m, n, k)[0]
+    assert A.min() >= 0 and A.max() <= 2.0 ** 64 and A.sum() <= 2.0 ** 100
+    if kind == "kl-top":
+        assert A.max() == 2.0 ** 64 and 0.2 < np.mean(A == 0) < 0.4
+    elif kind == "kl-tiny":
+        assert 2.0 ** -201 <= A.min() and A.max() < 2.0 ** -200
+    else:
+        e = np.frexp(A)[1]
+        assert e.min() <= -50 and e.max() >= 55 and A.min() >= 2.0 ** -60
+    wr.prefetch(kind, m, n, k, range(4))
+    for job in range(4):
+        _, W0, H0 = wr.case(kind, m, n, k, job)
+        ew, eh = wr.CORNER_SIGNS[job]
+        for X, ex in ((W0, ew), (H0, eh)):
+            assert 2.0 ** (ex - 1) <= X.min() and X.max() < 2.0 ** ex and 2.0 ** -60 <= X.min() and X.max() <= 2.0 ** 60
+        ref = wr.reference(kind, m, n, k, job)
+        for T in (1, 2):
+            Wo, Ho, it = oracle.brunet(A, W0, H0, T, 10 ** 6)
+            bh, bw = wr.bound_u(m, n, k, T)
+            eh_ = wr.cw_check(Ho, ref[T][1], bh, f"oracle H {kind} {m}x{n} k={k} job {job} T={T}")
+            ew_ = wr.cw_check(Wo, ref[T][0], bw, f"oracle W {kind} {m}x{n} k={k} job {job} T={T}")
+            print(f"{kind} {m}x{n} k={k} job {job} T={T}: H {eh_:.0f} u of {bh}, W {ew_:.0f} u of {bw}")
+            assert it == T
+
+
+CORNER_RANGE = [(kind, m, n, k) for kind, m, n, ks in wr.CORNER_CASES for k in ks if k in (2, 5, 16)]
+
+
+@pytest.mark.parametrize("kind,m,n,k", CORNER_RANGE, ids=[f"{c[0]}-{c[1]}x{c[2]}-k{c[3]}" for c in CORNER_RANGE])
+def test_kl_corner_reference_stays_in_range(kind, m, n, k):
+    """Over the T = 40 the GPU test runs: every VP, W and H of the long-double reference is finite and normal, and any
+    five VP values of the four factor-scale combinations (one batched reciprocal can hold restarts of all four) have a
+    product inside [2^-1021, 2^1021], the contract of brunet.hip's recip_batch."""
+    from concurrent.futures import ThreadPoolExecutor
+    A = wr.case(kind, m, n, k)[0]
+    with ThreadPoolExecutor(4) as ex:
+        runs = list(ex.map(lambda job: wr.ref_kl_range(A, *wr.case(kind, m, n, k, job)[1:], wr.CORNER_T), range(4)))
+    tiny, huge = np.finfo(np.float64).tiny, np.finfo(np.float64).max
+    vlo, vhi = min(r[2][0] for r in runs), max(r[2][1] for r in runs)
+    xlo, xhi = min(r[3][0] for r in runs), max(r[3][1] for r in runs)
+    print(f"{kind} {m}x{n} k={k}, T={wr.CORNER_T}: VP in [2^{float(np.log2(vlo)):.1f}, 2^{float(np.log2(vhi)):.1f}], "
+          f"W and H in [2^{float(np.log2(xlo)):.1f}, 2^{float(np.log2(xhi)):.1f}]")
+    for W, H, _, _ in runs:
+        assert np.isfinite(W).all() and np.isfinite(H).all()
+    assert tiny <= vlo and vhi <= huge and tiny <= xlo and xhi <= huge
+    assert 5 * float(np.log2(vlo)) >= -1021 and 5 * float(np.log2(vhi)) <= 1021
+    # the first update's VP values of the four combinations lie some 2^236 apart
+    first = [wr.case(kind, m, n, k, job)[1] @ wr.case(kind, m, n, k, job)[2] for job in (0, 3)]
+    assert np.log2(first[0].min() / first[1].max()) > 232

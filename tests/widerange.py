@@ -52,6 +52,10 @@ Where the recipe had to move to meet the conditions test_widerange_reference.py 
   * MU_W0_MK: above m k = 16384, W0 is scaled down to keep the H-side denominator on both sides of 1e-9.
   * KL_W0_SCALE: the KL factors times 2^20, to stay inside [2^-60, 2^60] under the batch scaling of 2^-32.
   * RESEED: ten (shape, k) cases take a later init seed, where the draw left one side's denominators one-sided.
+
+The KL corner cases (CORNER_*, below) are a second recipe: A and the caller factors at the ends of what
+nmfc_brunet_create and nmfc_brunet_run admit.  The same reference and the same bound apply: there is no subtraction, so
+the bound holds at any scale while everything stays normal, which test_widerange_reference.py asserts.
 """
 import functools
 
@@ -277,9 +281,71 @@ RESEED = {("mu", 37, 5, 5): 1, ("mu", 200, 16, 6): 1, ("mu", 200, 40, 5): 1, ("m
           ("mu", 3001, 150, 2): 5}
 
 
+# ---- the KL kernels at the corners of the domain they admit (test_gpu_widerange.py::test_kl_corners) -----------------
+# nmfc_brunet_create admits A up to 2^64 and nmfc_brunet_run caller factors in [2^-60, 2^60]: on the first update VP =
+# sum_c W H reaches about 2^+-118, and a group of restarts whose factors sit at opposite ends multiplies VP values some
+# 2^236 apart in one batched reciprocal (brunet.hip recip_batch).  Kinds "kl-top", "kl-tiny", "kl-mixed" name the matrix;
+# restart i of a batch takes the factor scales CORNER_SIGNS[i % 4], so every restart group of 2..5 holds both ends.
+# 129 x 37 and 64 x 5: partial 256-lane tiles, partial TL = 64 operand tiles on both sides, n below a wave's 8 samples.
+CORNER_KINDS = ("kl-top", "kl-tiny", "kl-mixed")
+CORNER_SIGNS = ((59, 59), (59, -59), (-59, 59), (-59, -59))      # exponents of (W0, H0)
+CORNER_KS = (2, 3, 4, 5, 6, 7, 8, 9, 10, 16)                     # every rank has its own RG / SPL / SL / RCP row
+CORNER_CASES = [(kind, m, n, ks) for kind in CORNER_KINDS for m, n, ks in ((129, 37, CORNER_KS), (64, 5, (2,)))]
+CORNER_T = 40    # on kl-tiny W grows by about m / n = 2^1.8 per iteration (eps decides both updates): not much longer
+
+
+@functools.lru_cache(maxsize=None)
+def corner_A(m, n, kind):
+    rng = _rng(SEED, m, n, CORNER_KINDS.index(kind), 3)
+    if kind == "kl-top":
+        A = np.minimum(2.0 ** 64 * rng.uniform(0.5, 1.0, (m, n)), 2.0 ** 64)
+        A[rng.random((m, n)) < 0.30] = 0.0
+        A[0, 0] = 2.0 ** 64                       # the bound itself
+    elif kind == "kl-tiny":
+        A = 2.0 ** -200 * rng.uniform(0.5, 1.0, (m, n))
+    else:
+        A = np.ldexp(rng.uniform(0.5, 1.0, (m, n)), rng.integers(-60 + 1, 64 + 1, (m, n)).astype(np.int32))
+    A = np.asfortranarray(A)
+    A.setflags(write=False)
+    return A
+
+
+@functools.lru_cache(maxsize=None)
+def corner_init(m, n, k, kind, job):
+    rng = _rng(SEED, m, n, k, CORNER_KINDS.index(kind), job, 4)
+    ew, eh = CORNER_SIGNS[job % 4]
+    W0 = np.asfortranarray(rng.uniform(0.5, 1.0, (m, k)) * 2.0 ** ew)
+    H0 = np.asfortranarray(rng.uniform(0.5, 1.0, (k, n)) * 2.0 ** eh)
+    W0.setflags(write=False)
+    H0.setflags(write=False)
+    return W0, H0
+
+
+def ref_kl_range(A, W0, H0, T):
+    """ref_kl that also returns the smallest and largest VP = (W H)[i, j] either update divides by, and the smallest
+    and largest entry of any W or H, over the T iterations."""
+    A, W, H = (np.asarray(x, dtype=LD) for x in (A, W0, H0))
+    e = LD(KL_EPS)
+    vp, wh = [np.inf, 0.0], [np.inf, 0.0]
+
+    def see(box, X):
+        box[0], box[1] = min(box[0], X.min()), max(box[1], X.max())
+    for _ in range(T):
+        P = W @ H
+        see(vp, P)
+        H = (H * (W.T @ (A / P)) + e) / W.sum(axis=0)[:, None]
+        P = W @ H
+        see(vp, P)
+        W = (W * ((A / P) @ H.T) + e) / H.sum(axis=1)[None, :]
+        see(wh, W), see(wh, H)
+    return W, H, tuple(vp), tuple(wh)
+
+
 def case(kind, m, n, k, job=0):
     """(A, W0, H0) of job `job` of the case (kind, m, n, k) as the tests run it.  For a batch, `job` is the restart's
     index among the restarts of its k: restart 0 of every k is the case whose conditions the CPU test asserts."""
+    if kind in CORNER_KINDS:
+        return (corner_A(m, n, kind),) + corner_init(m, n, k, kind, job)
     return (wide_A(m, n, SEED, kind),) + wide_init(m, n, k, case_seed(kind, m, n, k), kind, job)
 
 
