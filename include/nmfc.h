@@ -118,6 +118,24 @@ int nmfc_engine_residuals(nmfc_engine* e, double* dnorm_out);
  * these nk jobs are copied off the device.  Returns nk, or -1 as nmfc_engine_residuals. */
 int nmfc_engine_best(nmfc_engine* e, int32_t* best_job_out, double* best_dnorm_out, double* W_out, double* H_out);
 
+/* The BROAD / GenePattern nmfconsensus script's Euclidean NMF() (error.function = "euclidean") on the MFMA engine.
+ * enable != 0: later nmfc_engine_run calls run, per job and per iteration t = 1, 2, ...,
+ *     H <- H * ((W^T A) / ((W^T W) H)) + eps        divide, multiply, add
+ *     W <- ((W * (A H^T)) / (W (H H^T))) + eps      multiply, divide, add       eps = 2^-52 (.Machine$double.eps)
+ * with no zero guard and no clamp (IEEE results as R's; the denominators come from the Gram matrices, the m x n product
+ * W H is never formed), and stop by the script's membership rule: whenever t % stopfreq == 0 the 1-based first row of
+ * every sample's maximum of H is compared with the previous check's (all 0 before the first check, which therefore
+ * always counts as a change); stopconv unchanged checks in a row stop the job, whose W is still updated in that
+ * iteration.  stopped_early is 1 whenever the rule fired, also at t = maxiter.
+ * opts->stop_rule: NMFC_STOP_FIXED runs exactly maxiter iterations; EVERY other value, the default of
+ * nmfc_default_opts included, means the membership rule (the nmf_mu rules do not apply to this update).
+ * The job seed is seed + restart (restart 1-based, nmfconsensus's set.seed(rseed + i): the same for every k) for either
+ * init stream; jobs keep the engine's order (k fastest), job_begin / job_end, W_init / H_init, the residual pass and
+ * nmfc_engine_best work as in every other run.  The sweep always takes the MFMA kernels (never the small-shape or solo
+ * ones), so a job's bits depend on (A, k, seed, options) only.  enable == 0 restores the nmf_mu runs exactly (stopconv and
+ * stopfreq are ignored then).  Returns 0, or -1 (nmfc_last_error) for a NULL engine, stopconv < 1 or stopfreq < 1. */
+int nmfc_engine_set_euclid(nmfc_engine* e, int enable, int stopconv, int stopfreq);
+
 /* Convenience: create, run, destroy. */
 /* One restart of nmf_mu (nmf_mu.c:84-315) on the small-shape team kernel (m rounded up to 128 <= 8192, n <= 64,
  * k <= 16), with one upload, one launch and one download: the per-call path of the nmf_mu drop-in (nmf.r:41-45).

@@ -4,8 +4,10 @@ Host mirror of the BROAD `nmfconsensus(...)` R script that the reference names (
 test_nmf.r:29) but does not ship.  Names and argument meaning follow that script:
 
   NMF_div(V, k, maxniter, seed, stopconv, stopfreq)      NMF.div: one Brunet KL-divergence restart
+  NMF(V, k, maxniter, seed, stopconv, stopfreq)          NMF: one Euclidean (Frobenius) MU restart
   nmfconsensus(input_ds, k_init, k_final, num_clusterings, maxniter, error_function="divergence",
                rseed=123456789, stopconv=40, stopfreq=10)  the k sweep + consensus + cophenetic
+                                                          (error_function "divergence" or "euclidean")
 
 Every compute step calls nmfconsensus_amd/libnmf.so (nmfc_brunet_*, HIP gfx950); there is no CPU
 fallback.  Restart i (1-based) of every k runs set.seed(rseed + i) then W <- runif(m k), H <- runif(k n)
@@ -13,6 +15,10 @@ fallback.  Restart i (1-based) of every k runs set.seed(rseed + i) then W <- run
 by the consensus) is not computed; its value for the factors a run returns is (want_divergence, want_best: one device
 pass per k batch, and only each k's best restart's factors leave the GPU).  Parity vs the reference is unpinned (the script is not in the
 reference); the oracle is oracle/brunet_oracle.c.
+
+error_function="euclidean" runs the script's NMF() on the fp64-MFMA engine of nmf.Engine (nmfc_engine_set_euclid:
+the same three matrix products per iteration as nmf_mu, the script's elementwise rule, membership stop rule and
+set.seed(rseed + i) seeding); DESIGN.md "Euclidean NMF()" restates the algorithm.
 """
 from __future__ import annotations
 
@@ -24,7 +30,7 @@ from . import _lib
 from ._lib import BrunetOpts, Result
 from .nmf import SweepResult, computeConsensusAndSaveFiles
 
-__all__ = ["BrunetEngine", "NMF_div", "nmfconsensus"]
+__all__ = ["BrunetEngine", "NMF_div", "NMF", "nmfconsensus"]
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -224,17 +230,74 @@ def NMF_div(V, k: int, maxniter: int = 2000, seed: int = 123456, stopconv: int =
     return out
 
 
+def _euclid_sweep(A, ks, R: int, *, maxiter: int, seed: int, stopconv: int, stopfreq: int, device: int = -1,
+                  want_factors: bool = False, want_counts: bool = True, want_error: bool = False,
+                  want_best: bool = False) -> SweepResult:
+    """The Euclidean NMF() sweep on the MU engine, its per-job arrays reordered from the engine's job order (k
+    fastest: job = restart * nk + k index) into nmfconsensus order (for k in ks: for restart i)."""
+    from .nmf import Engine, INIT_R_RUNIF, LABEL_ARGMAX, STOP_REF_COMPAT
+
+    ks = [int(k) for k in ks]
+    nk = len(ks)
+    with Engine(A, device) as eng:
+        m, n = eng.m, eng.n
+        # any stop rule but STOP_FIXED means NMF()'s membership rule in this mode
+        r = eng.run(ks, R, maxiter=maxiter, seed=seed, stop_rule=STOP_REF_COMPAT, label_rule=LABEL_ARGMAX,
+                    init_stream=INIT_R_RUNIF, want_factors=want_factors, want_counts=want_counts,
+                    want_residuals=want_error, want_best=want_best, euclid=dict(stopconv=stopconv, stopfreq=stopfreq))
+    perm = np.array([i * nk + g for g in range(nk) for i in range(R)], dtype=np.int64)
+    scale = 1.0 / np.sqrt(float(m) * float(n))   # error.v = ||V - W H||_F / (m n) = dnorm / sqrt(m n)
+    out = SweepResult(ks=ks, R=R, n=n, counts=r.counts, consensus=r.consensus, labels=r.labels[perm],
+                      iters=r.iters[perm], stopped_early=r.stopped_early[perm],
+                      W=[r.W[j] for j in perm] if r.W is not None else None,
+                      H=[r.H[j] for j in perm] if r.H is not None else None, seconds_total=r.seconds_total,
+                      seconds_iterate=r.seconds_iterate, restart_iterations=r.restart_iterations,
+                      max_iter_run=r.max_iter_run, job_begin=0, job_end=R)
+    if r.dnorm is not None:
+        out.error = (r.dnorm[perm] * scale).reshape(nk, R)
+    if want_best:
+        out.best_restart = [r.best[k]["job"] // nk for k in ks]
+        out.best_error = [r.best[k]["dnorm"] * scale for k in ks]
+        out.best_W = [r.best[k]["W"] for k in ks]
+        out.best_H = [r.best[k]["H"] for k in ks]
+    return out
+
+
+def NMF(V, k: int, maxniter: int = 2000, seed: int = 123456, stopconv: int = 40, stopfreq: int = 10,
+        device: int = -1, want_error: bool = False) -> dict:
+    """NMF: one Euclidean MU restart of the BROAD script from set.seed(seed).  Returns dict(W, H, t); with want_error
+    also 'error', error.v of the returned factors: sqrt(sum((V - W H)^2)) / (m n)."""
+    # restart i = 1 of a one-restart sweep runs set.seed(rseed + 1)
+    r = _euclid_sweep(_f64(V), [k], 1, maxiter=maxniter, seed=seed - 1, stopconv=stopconv, stopfreq=stopfreq,
+                      device=device, want_factors=True, want_counts=False, want_error=want_error)
+    out = {"W": r.W[0], "H": r.H[0], "t": int(r.iters[0])}
+    if r.error is not None:
+        out["error"] = float(r.error[0, 0])
+    return out
+
+
 def nmfconsensus(input_ds, k_init: int, k_final: int, num_clusterings: int, maxniter: int,
                  error_function: str = "divergence", rseed: int = 123456789, directory: str | None = None,
                  stopconv: int = 40, stopfreq: int = 10, doc_string: str = "", device: int = -1,
-                 want_divergence: bool = False, want_best: bool = False) -> dict:
+                 want_divergence: bool = False, want_best: bool = False, want_error: bool = False) -> dict:
     """The BROAD consensus sweep: for k in k_init..k_final, num_clusterings Brunet restarts, membership
     = argmax of each H column, connectivity summed and divided by num_clusterings, then the cophenetic
     correlation, ordering and cutree membership (computeConsensusAndSaveFiles).  input_ds is an m x n
     array or a .gct path.  want_divergence adds 'divergence', (nk, num_clusterings); want_best adds that and 'best',
-    {k: dict(restart=<0-based>, divergence=, W=<m x k>, H=<k x n>)}: the best metagenes per k."""
-    if error_function != "divergence":
-        raise NotImplementedError("only error_function='divergence' (Brunet KL MU) is implemented")
+    {k: dict(restart=<0-based>, divergence=, W=<m x k>, H=<k x n>)}: the best metagenes per k.
+
+    error_function="euclidean": the restarts are the script's NMF() (Frobenius objective) instead of NMF.div, with the
+    same outputs.  want_error adds 'error', (nk, num_clusterings): error.v of every restart's final factors,
+    sqrt(sum((V - W H)^2)) / (m n); want_best adds that and 'best', {k: dict(restart=, error=, W=, H=)}, per k the
+    restart with the smallest error (the lowest on ties).  want_divergence is refused there (and want_error with
+    "divergence")."""
+    if error_function not in ("divergence", "euclidean"):
+        raise ValueError("error_function must be 'divergence' or 'euclidean'")
+    euclid = error_function == "euclidean"
+    if euclid and want_divergence:
+        raise ValueError("want_divergence belongs to error_function='divergence'; use want_error")
+    if not euclid and want_error:
+        raise ValueError("want_error belongs to error_function='euclidean'; use want_divergence")
     if k_init < 2 or k_final < k_init:
         raise ValueError("need 2 <= k_init <= k_final")
     if isinstance(input_ds, str):
@@ -243,12 +306,23 @@ def nmfconsensus(input_ds, k_init: int, k_final: int, num_clusterings: int, maxn
     else:
         A = input_ds
     ks = list(range(k_init, k_final + 1))
-    with BrunetEngine(A, device) as eng:
-        sw = eng.run(ks, num_clusterings, maxiter=maxniter, seed=rseed, stopconv=stopconv, stopfreq=stopfreq,
-                     want_divergence=want_divergence, want_best=want_best)
+    if euclid:
+        sw = _euclid_sweep(_f64(A), ks, num_clusterings, maxiter=maxniter, seed=rseed, stopconv=stopconv,
+                           stopfreq=stopfreq, device=device, want_error=want_error or want_best, want_best=want_best)
+    else:
+        with BrunetEngine(A, device) as eng:
+            sw = eng.run(ks, num_clusterings, maxiter=maxniter, seed=rseed, stopconv=stopconv, stopfreq=stopfreq,
+                         want_divergence=want_divergence, want_best=want_best)
     result = {str(k): sw.consensus[i] for i, k in enumerate(ks)}
     out = computeConsensusAndSaveFiles(result, save_dir=directory, doc_string=doc_string)
     out["sweep"] = sw
+    if euclid:
+        if want_error or want_best:
+            out["error"] = sw.error
+        if want_best:
+            out["best"] = {k: dict(restart=sw.best_restart[i], error=sw.best_error[i], W=sw.best_W[i], H=sw.best_H[i])
+                           for i, k in enumerate(ks)}
+        return out
     if want_divergence or want_best:
         out["divergence"] = sw.divergence
     if want_best:

@@ -343,6 +343,9 @@ struct nmfc_engine {
     long long ahtw_narrow = 0, ahtw_128 = 0, ahtw_64 = 0;                                         // ... per A h^T form
   } info;
   std::string info_str;
+  // nmfc_engine_set_euclid: runs use the BROAD script's Euclidean NMF() rules, stop rule and seeding
+  bool euclid = false;
+  int euc_stopconv = 40, euc_stopfreq = 10;
   // nmfc_engine_set_residuals: the residual pass of the results phase.  ssq: sum of d^2 per shard job of the last
   // run (device, and h_ssq on the host); respart: its per-(job, tile) partials.  last_*: what the getters need of that
   // run (the archive Wfin / Hfin lives until the next one): the shard, and each shard job's first archive row
@@ -700,8 +703,18 @@ int check_args(Sweep& s, nmfc_engine* e, const int* ks, int nk, int R, const nmf
     set_err("nmfc_engine_run: bad stop rule, label rule or init stream");
     return -1;
   }
+  // nmfc_engine_set_euclid: FIXED means fixed, every other value (the default included) the script's membership rule
+  if (e->euclid) opts.stop_rule = opts.stop_rule == NMFC_STOP_FIXED ? STOP_FIXED : STOP_MEMBER;
   HCHECK(hipSetDevice(e->dev));
   return 0;
+}
+
+// The job seed of shard slot `slot`: BatchJobs' seed + job_id - 1 (nmf.r), or, for the Euclidean NMF() sweep,
+// nmfconsensus's set.seed(rseed + i) of the job's 1-based restart i (jobs are k fastest, so i = job / nk + 1): the same
+// seed for every k.
+uint32_t job_seed(const Sweep& s, int slot) {
+  const long job = s.jb + slot;
+  return (uint32_t)(s.opts.seed + (uint32_t)(s.e->euclid ? job / s.nk + 1 : job));
 }
 
 // The shard's job range, restart ids, the small / solo split and the first packing; no device work.
@@ -737,7 +750,7 @@ int plan_jobs(Sweep& s) {
   }
   // small shapes: one persistent workgroup per 16-column block runs the whole loop (a function of m, n and
   // the stop rule only, so a job takes the same path -- and gives the same bits -- in any batch)
-  s.small = e->small_ok && e->m_pad <= 1024 && n <= 64 && s.opts.stop_rule != NMFC_STOP_TOLX;
+  s.small = e->small_ok && e->m_pad <= 1024 && n <= 64 && s.opts.stop_rule != NMFC_STOP_TOLX && !e->euclid;
   // ... and there, a restart the solo kernels take (rank 2..8 on gct-sized shapes, nmfc_mu_solo_fits: k_solo_mu for
   // ranks 2..4, k_solo8_mu for 5..8) runs on one workgroup of its own, the others in k_small_mu blocks; the choice is a
   // function of (m, n, k) only, so a job gives the same bits in any batch and on any number of GPUs.  Through the
@@ -840,7 +853,7 @@ int init_r_runif(Sweep& s) {
   std::vector<InitJob> ij(nj);
   for (int i = 0; i < nj; ++i) {
     const RestartInfo& r = s.pk.ri[i];
-    ij[i] = InitJob{(uint32_t)(s.opts.seed + (uint32_t)(s.jb + s.rslot[r.rid])), r.col0, r.k, 0};
+    ij[i] = InitJob{job_seed(s, s.rslot[r.rid]), r.col0, r.k, 0};
   }
   if (e->initjobs.ensure(sizeof(InitJob) * nj)) return -1;
   HCHECK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
@@ -873,7 +886,7 @@ int init_glibc(Sweep& s) {
     const RestartInfo& r = pk.ri[i];
     const long total = (long)m * r.k + (long)r.k * n;
     const int nch = (int)((total + rchunk - 1) / rchunk);
-    ij[i].seed = (uint32_t)(s.opts.seed + (uint32_t)(s.jb + s.rslot[r.rid]));   // job seed = seed + job_id - 1
+    ij[i].seed = job_seed(s, s.rslot[r.rid]);   // job seed = seed + job_id - 1
     ij[i].col0 = r.col0;
     ij[i].k = r.k;
     ij[i].nchunks = nch;
@@ -1040,6 +1053,7 @@ int small_phase(Sweep& s) {
 // every k_wta2 / full-width k_ahtw4 instantiation has its template's one signature
 using Wta2Kernel = decltype(&k_wta2<1, 64, 2, 2, 1, GT_NBUF, 1, true, true, true>);
 using AhtwKernel = decltype(&k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE>);
+using AhtwKernelE = decltype(&k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, false, RULE_EUCLID>);   // Euclidean NMF() rule
 
 // narrow (end-of-sweep) W^T A: the restarts block-packed into the first nblk 16-column blocks
 void launch_wta_narrow(const Sweep& s, int nblk) {
@@ -1148,6 +1162,7 @@ struct ChunkPlan {
                    // workgroups (each would fetch a prologue stage before finding its panel idle)
   int ngt_ahtw, grid_ahtw;
   AhtwKernel ka;   // the full-width A h^T tile
+  AhtwKernelE kae; // ... with the Euclidean NMF() W rule (nmfc_engine_set_euclid)
 };
 
 int launch_wta(Sweep& s, const ChunkPlan& cp, int* gsplit) {
@@ -1163,6 +1178,16 @@ int launch_wta(Sweep& s, const ChunkPlan& cp, int* gsplit) {
 
 void launch_hupdate(const Sweep& s, int iter, int gsplit) {
   nmfc_engine* e = s.e;
+  if (e->euclid) {   // the Euclidean NMF() rule and its membership check (nmfc_engine_set_euclid)
+    const StopMember stop{s.opts.stop_rule, e->euc_stopconv, e->euc_stopfreq};
+    hipLaunchKernelGGL((k_hupdate<32, 4, RULE_EUCLID>), dim3(s.nact), dim3(NTH), 0, e->st, iter, s.opts.maxiter, stop,
+                       e->rinfo.as<RestartInfo>(), e->n, e->n_pad, e->Gpart.as<double>(), s.g_ld, s.g_split, gsplit,
+                       e->nsplit, e->SWpart.as<double>(), s.sw_total, e->H[s.cur].as<double>(), e->SH.as<double>(),
+                       e->stop_iter.as<int>(), e->stop_reason.as<int>(), e->unchanged.as<int>(),
+                       e->classes.as<int>(), s.cls_ld, e->n_stopped.as<int>(), e->SHP.as<double>(),
+                       e->colact.as<int>(), e->Hstat.as<double>());
+    return;
+  }
   hipLaunchKernelGGL(k_hupdate<>, dim3(s.nact), dim3(NTH), 0, e->st, iter, s.opts.maxiter, s.opts.stop_rule,
                      e->rinfo.as<RestartInfo>(), e->n, e->n_pad, e->Gpart.as<double>(), s.g_ld, s.g_split, gsplit,
                      e->nsplit, e->SWpart.as<double>(), s.sw_total, e->H[s.cur].as<double>(), e->SH.as<double>(),
@@ -1174,6 +1199,18 @@ void launch_hupdate(const Sweep& s, int iter, int gsplit) {
 void launch_ahtw(const Sweep& s, const ChunkPlan& cp, int iter) {
   nmfc_engine* e = s.e;
   ++(cp.nblk > 0 ? e->info.ahtw_narrow : cp.tc.ahtw_small ? e->info.ahtw_64 : e->info.ahtw_128);
+  if (e->euclid) {   // the same grids, the Euclidean NMF() W rule; the kernels also take m (padded gene rows stay +0.0)
+    if (cp.nblk > 0)
+      hipLaunchKernelGGL((k_ahtw4<GT / 4, GT_NBUF, 1, 16, 2, false, false, RULE_EUCLID>), dim3(4 * e->ngt * cp.nblk),
+                         dim3(128), 0, e->st, iter, e->H[s.cur].as<double>(), e->n_pad, e->Arm.as<double>(), e->m_pad,
+                         e->W[s.cur].as<double>(), e->SHP.as<double>(), e->colinfo.as<ColInfo>(),
+                         e->colact.as<int>(), cp.nblk, GeneTiles{4 * e->ngt, e->m});
+    else
+      hipLaunchKernelGGL(cp.kae, dim3(cp.grid_ahtw), dim3(256), 0, e->st, iter, e->H[s.cur].as<double>(), e->n_pad,
+                         e->Arm.as<double>(), e->m_pad, e->W[s.cur].as<double>(), e->SHP.as<double>(),
+                         e->colinfo.as<ColInfo>(), e->colact.as<int>(), cp.lp, GeneTiles{cp.ngt_ahtw, e->m});
+    return;
+  }
   if (cp.nblk > 0)   // per live 16-column block: 16 rows x 32 genes, 2 waves
     hipLaunchKernelGGL((k_ahtw4<GT / 4, GT_NBUF, 1, 16, 2>), dim3(4 * e->ngt * cp.nblk), dim3(128), 0, e->st,
                        iter, e->H[s.cur].as<double>(), e->n_pad, e->Arm.as<double>(), e->m_pad,
@@ -1200,6 +1237,11 @@ ChunkPlan plan_chunk(const Sweep& s) {
                                  : k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE>)
                            : (kh ? k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2>
                                  : k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE>);
+  constexpr int RE = RULE_EUCLID;
+  cp.kae = cp.tc.ahtw_small ? (kh ? k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2, RE>
+                                  : k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, false, RE>)
+                            : (kh ? k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2, RE>
+                                  : k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, false, RE>);
   return cp;
 }
 
@@ -1674,6 +1716,23 @@ void nmfc_engine_set_timing(nmfc_engine* e, int enable) {
 
 void nmfc_engine_set_residuals(nmfc_engine* e, int enable) {
   if (e) e->residuals = enable != 0;
+}
+
+int nmfc_engine_set_euclid(nmfc_engine* e, int enable, int stopconv, int stopfreq) {
+  if (!e) {
+    set_err("nmfc_engine_set_euclid: no engine");
+    return -1;
+  }
+  if (enable && (stopconv < 1 || stopfreq < 1)) {
+    set_err("nmfc_engine_set_euclid: stopconv = %d and stopfreq = %d must both be >= 1", stopconv, stopfreq);
+    return -1;
+  }
+  e->euclid = enable != 0;
+  if (enable) {
+    e->euc_stopconv = stopconv;
+    e->euc_stopfreq = stopfreq;
+  }
+  return 0;
 }
 
 namespace {

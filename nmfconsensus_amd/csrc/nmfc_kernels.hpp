@@ -42,6 +42,57 @@ __device__ __forceinline__ double mu_rule(double old, double num, double den) {
   return t < 0.0 ? 0.0 : t;
 }
 
+// The BROAD nmfconsensus script's Euclidean NMF() (DESIGN.md "Euclidean NMF()"): the second elementwise rule the H and
+// W update kernels can be instantiated with, and its stop rule (every stopfreq-th iteration the per-sample first-maximum
+// class against the stored one; stopconv unchanged checks in a row stop the restart).
+constexpr int RULE_MU = 0, RULE_EUCLID = 1;
+constexpr int STOP_MEMBER = 4;                          // internal to the engine: set by nmfc_engine_set_euclid runs
+constexpr double R_EPS = 2.220446049250313080847e-16;   // R's .Machine$double.eps = 2^-52
+
+// H <- H * (crossprod(W, V) / crossprod(W, VP)) + eps: divide, multiply, add, each rounded on its own (no FMA
+// contraction); no zero guard and no clamp, so the IEEE results are R's.
+__device__ __forceinline__ double euclid_rule_h(double old, double num, double den) {
+#pragma clang fp contract(off)
+  const double q = num / den;
+  const double t = old * q;
+  return t + R_EPS;
+}
+
+// W <- W * (V %*% t(H)) / (VP %*% t(H)) + eps: multiply, divide, add.
+__device__ __forceinline__ double euclid_rule_w(double old, double num, double den) {
+#pragma clang fp contract(off)
+  const double t = old * num;
+  const double q = t / den;
+  return q + R_EPS;
+}
+
+// Kernel arguments only the Euclidean instantiations take: they stand in the place of an int of the default rule's
+// signature, which therefore stays as it is.
+struct StopMember {
+  int rule, stopconv, stopfreq;   // STOP_FIXED or STOP_MEMBER, and the script's stopconv / stopfreq
+};
+struct GeneTiles {
+  int ngt, m;   // gene tiles of the launch, and the rows of A: W rows >= m are padding and stay +0.0
+};
+template <int RULE>
+struct RuleArgs {
+  using Stop = int;
+  using Tiles = int;
+};
+template <>
+struct RuleArgs<RULE_EUCLID> {
+  using Stop = StopMember;
+  using Tiles = GeneTiles;
+};
+__device__ __forceinline__ int stop_rule_of(int s) { return s; }
+__device__ __forceinline__ int stop_rule_of(const StopMember& s) { return s.rule; }
+__device__ __forceinline__ int stopconv_of(int) { return 200; }   // nmf_mu.c:269
+__device__ __forceinline__ int stopconv_of(const StopMember& s) { return s.stopconv; }
+__device__ __forceinline__ int stopfreq_of(int) { return 2; }     // nmf_mu.c:253
+__device__ __forceinline__ int stopfreq_of(const StopMember& s) { return s.stopfreq; }
+__device__ __forceinline__ int ngt_of(int t) { return t; }
+__device__ __forceinline__ int ngt_of(const GeneTiles& t) { return t.ngt; }
+
 // The wave's index in its workgroup as a wave-uniform (SGPR) value.  threadIdx.x >> 6 is uniform within a wave, but the
 // compiler does not know it: a buffer resource or a base pointer derived from it would be kept in VGPRs and every
 // buffer load / store through it wrapped in a readfirstlane "waterfall" loop (round 5: 64 such loops around k_ahtw4's
@@ -1272,8 +1323,12 @@ struct HupdSmem {
 // partials of one sample are loaded GS chunks at a time (GS*K <= 64 values in flight per thread).  The
 // arithmetic order is fixed: chunk partials and Gram partials summed in chunk order, d = sum_b in b order,
 // h h^T by T = f(k) threads per pair over j = pq (mod T) in j order, then the T partials in pq order.
-template <int K, int GSV = 32>
-__device__ __forceinline__ void hupdate_body(const RestartInfo me, int iter, int maxiter, int stop_rule, int n,
+// RULE_EUCLID: euclid_rule_h instead of mu_rule, and the membership check (STOP_MEMBER) instead of the four nmf_mu
+// rules: on iterations that are multiples of stopfreq, the 1-based first-maximum row of every sample against the stored
+// one (the zeroed classes row is R's old.membership <- 0, so the first check always counts as a change).
+template <int K, int GSV = 32, int RULE = RULE_MU>
+__device__ __forceinline__ void hupdate_body(const RestartInfo me, int iter, int maxiter, int stop_rule, int stopconv,
+                                             int stopfreq, int n,
                                              long n_pad, const double* __restrict__ Gpart, long g_ld, long g_split,
                                              int gsplit, int nsplit, const double* __restrict__ SWpart, long sw_total,
                                              double* __restrict__ H, double* __restrict__ SH,
@@ -1294,13 +1349,16 @@ __device__ __forceinline__ void hupdate_body(const RestartInfo me, int iter, int
   const int tid = threadIdx.x;
   constexpr int k = K;
   const int c0 = me.col0;
-  const bool check = (stop_rule != STOP_FIXED) && iter > 1 && (iter % 2 == 0);
-  const bool tolx = check && stop_rule == STOP_TOLX;
+  constexpr bool EUC = RULE == RULE_EUCLID;
+  const bool check = EUC ? (stop_rule == STOP_MEMBER && iter % stopfreq == 0)
+                         : ((stop_rule != STOP_FIXED) && iter > 1 && (iter % 2 == 0));
+  const bool tolx = !EUC && check && stop_rule == STOP_TOLX;
+  constexpr int CLS0 = EUC ? 1 : 0;   // stored class of row 0: 1-based for the membership rule (0 = none yet)
   double tdm = 0.0, tom = 0.0;   // this thread's max |h0 - h| and max |h0| (STOP_TOLX)
   // stop state, loaded now and used at the end
   const int u_prev = (tid == 0 && check) ? unchanged[rid] : 0;
   const int nwin = k < n ? k : n;
-  const bool refc = check && stop_rule == STOP_REF_COMPAT;
+  const bool refc = !EUC && check && stop_rule == STOP_REF_COMPAT;
   const int cl_prev = (refc && tid < nwin) ? classes[(long)rid * cls_ld + tid] : 0;
   // the sample rounds' loads: H and the split-K partials of W^T A (first group issued here)
   auto load_h = [&](int j, double* hc) {
@@ -1372,7 +1430,7 @@ __device__ __forceinline__ void hupdate_body(const RestartInfo me, int iter, int
     int cl_j = 0;
     if (valid) {
       load_h(j, hc);
-      if (check && stop_rule == STOP_ARGMAX_STABLE) cl_j = classes[(long)rid * cls_ld + j];
+      if ((EUC ? check : (check && stop_rule == STOP_ARGMAX_STABLE))) cl_j = classes[(long)rid * cls_ld + j];
       sum_g(j, gs);
     }
     __syncthreads();   // sw, win (first round) / Hn free (later rounds)
@@ -1385,7 +1443,10 @@ __device__ __forceinline__ void hupdate_body(const RestartInfo me, int iter, int
         double d = 0.0;
 #pragma unroll
         for (int bb = 0; bb < K; ++bb) d = fma(sw[a * KMAX + bb], hc[bb], d);
-        hn = mu_rule(hc[a], gs[a], d);
+        if constexpr (EUC)
+          hn = euclid_rule_h(hc[a], gs[a], d);
+        else
+          hn = mu_rule(hc[a], gs[a], d);
         H[(long)(c0 + a) * n_pad + j] = hn;
         if (tolx) {   // calculateMaxchange(h, h0) (calculatemaxchange.c:55-60): dlange('M') of h0 and h0 - h
           tdm = fmax(tdm, fabs(hc[a] - hn));
@@ -1405,8 +1466,8 @@ __device__ __forceinline__ void hupdate_body(const RestartInfo me, int iter, int
         bestv = hn;
       }
     }
-    if (check && stop_rule == STOP_ARGMAX_STABLE && valid && cl_j != best) {
-      classes[(long)rid * cls_ld + j] = best;
+    if ((EUC ? check : (check && stop_rule == STOP_ARGMAX_STABLE)) && valid && cl_j != best + CLS0) {
+      classes[(long)rid * cls_ld + j] = best + CLS0;
       changed = 1;
     }
     __syncthreads();
@@ -1464,7 +1525,7 @@ __device__ __forceinline__ void hupdate_body(const RestartInfo me, int iter, int
       if (!changed) {
         const int u = u_prev + 1;
         unchanged[rid] = u;
-        if (u >= 200) reason = 1;   // nmf_mu.c:269-271
+        if (u >= stopconv) reason = 1;   // nmf_mu.c:269-271 (200) / the script's stopconv
       } else {
         unchanged[rid] = 0;
       }
@@ -1479,8 +1540,8 @@ __device__ __forceinline__ void hupdate_body(const RestartInfo me, int iter, int
 }
 
 // <32, 4>: 4 waves per SIMD, two 512-thread workgroups per CU (full-load launch 150 -> 118 us).
-template <int GSV = 32, int MINW = 4>
-static __global__ __launch_bounds__(NTH, MINW) void k_hupdate(int iter, int maxiter, int stop_rule,
+template <int GSV = 32, int MINW = 4, int RULE = RULE_MU>
+static __global__ __launch_bounds__(NTH, MINW) void k_hupdate(int iter, int maxiter, typename RuleArgs<RULE>::Stop stop,
                                                         const RestartInfo* __restrict__ ri, int n, long n_pad,
                                                         const double* __restrict__ Gpart, long g_ld, long g_split,
                                                         int gsplit, int nsplit, const double* __restrict__ SWpart,
@@ -1496,7 +1557,7 @@ static __global__ __launch_bounds__(NTH, MINW) void k_hupdate(int iter, int maxi
   if (stop_iter[me.rid] != 0) return;
 #define NMFC_HUPD_CASE(KK)                                                                                      \
   case KK:                                                                                                     \
-    hupdate_body<KK, GSV>(me, iter, maxiter, stop_rule, n, n_pad, Gpart, g_ld, g_split, gsplit, nsplit, SWpart, sw_total, H, SH, \
+    hupdate_body<KK, GSV, RULE>(me, iter, maxiter, stop_rule_of(stop), stopconv_of(stop), stopfreq_of(stop), n, n_pad, Gpart, g_ld, g_split, gsplit, nsplit, SWpart, sw_total, H, SH, \
                      stop_iter, stop_reason, unchanged, classes, cls_ld, n_stopped, SHP, colact, Hstat, sm);   \
     break;
   switch (me.k) {
@@ -1553,14 +1614,19 @@ static constexpr int ahtw4_lds() {
   return GTile<PR * NPT, GTG, NPT, WC, NBUF>::LDS_BYTES + (LATE ? 0 : NPT * PR * KMAX * 8);
 }
 // KHALF: the last K stage's second half is padding (n_pad - n >= 8, decided on the host): skipped.
-template <int GTG = GT, int NBUF = GT_NBUF, int NPT = 1, int PR = PANEL, int WC = 4, bool LATE = false, bool KHALF = false>
+// RULE_EUCLID: euclid_rule_w instead of mu_rule_sel.  That rule has no zero guard, so a padded gene row (gene >= m,
+// all of old, num and den zero) would become 0 * 0 / 0 + eps = NaN and poison W^T W: the epilogue masks by the gene
+// index (the kernel receives m beside ngt) and writes +0.0 there; a real row follows the rule whatever it holds.
+template <int GTG = GT, int NBUF = GT_NBUF, int NPT = 1, int PR = PANEL, int WC = 4, bool LATE = false, bool KHALF = false,
+          int RULE = RULE_MU>
 static __global__ __launch_bounds__(64 * NPT * WC,
                                     (163840 / ahtw4_lds<GTG, NBUF, NPT, PR, WC, LATE>()) * NPT * WC / 4 > 8
                                         ? 8
                                         : (163840 / ahtw4_lds<GTG, NBUF, NPT, PR, WC, LATE>()) * NPT * WC / 4)
 void k_ahtw4(int iter, const double* __restrict__ H, long n_pad, const double* __restrict__ Arm, long m_pad,
              double* __restrict__ W, const double* __restrict__ SHP, const ColInfo* __restrict__ ci,
-             const int* __restrict__ colact, int npanels, int ngt) {
+             const int* __restrict__ colact, int npanels, typename RuleArgs<RULE>::Tiles tiles) {
+  const int ngt = ngt_of(tiles);
   using TileW4 = GTile<PR * NPT, GTG, NPT, WC, NBUF>;
   constexpr int AHTW4_SH = TileW4::LDS_BYTES;
   constexpr int AHTW4_LDS = ahtw4_lds<GTG, NBUF, NPT, PR, WC, LATE>();
@@ -1709,7 +1775,13 @@ void k_ahtw4(int iter, const double* __restrict__ H, long n_pad, const double* _
       if (!((actmask >> c) & 1)) continue;
 #pragma unroll
       for (int nb = 0; nb < TileW4::NB; ++nb) {
-        const double v = mu_rule_sel(w0[mb][nb][reg], tl.acc[mb][nb][reg], e[nb][reg]);
+        double v;
+        if constexpr (RULE == RULE_EUCLID) {
+          const int gene = gt * GTG + (GTG / WC) * wc + 16 * nb + (lane & 15);
+          v = gene < tiles.m ? euclid_rule_w(w0[mb][nb][reg], tl.acc[mb][nb][reg], e[nb][reg]) : 0.0;
+        } else {
+          v = mu_rule_sel(w0[mb][nb][reg], tl.acc[mb][nb][reg], e[nb][reg]);
+        }
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rw, wvoff, woff(mb, reg, nb), 0);
       }
     }

@@ -88,6 +88,9 @@ class SweepResult:
     best_divergence: list | None = None        # per k: its divergence
     best_W: list | None = None                 # per k: its W (m x k)
     best_H: list | None = None                 # per k: its H (k x n)
+    # brunet.nmfconsensus(error_function="euclidean"): NMF()'s error.v of the final factors, sqrt(sum((V - W H)^2)) / (m n)
+    error: np.ndarray | None = None            # (nk, R) float64
+    best_error: list | None = None             # per k: the smallest (best_restart: its restart, the lowest on ties)
 
 
 class Engine:
@@ -113,6 +116,7 @@ class Engine:
         self._last_ks, self._last_nj = [], 0
         self.device = self.L.nmfc_engine_device(h)   # HIP ordinal resolved at creation (device -1: the current one)
         self._residuals = False
+        self._euclid = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -139,6 +143,15 @@ class Engine:
         """Later run() calls compute every job's residual norm in the results phase (nmfc_engine_set_residuals)."""
         self._residuals = bool(on)
         self.L.nmfc_engine_set_residuals(self.h, 1 if on else 0)
+
+    def set_euclid(self, on: bool, stopconv: int = 40, stopfreq: int = 10):
+        """Later run() calls use the BROAD script's Euclidean NMF() update, its membership stop rule (stopconv
+        unchanged checks in a row, one check every stopfreq iterations; stop_rule=STOP_FIXED still means exactly
+        maxiter iterations, every other value the membership rule) and its seeding, job seed = seed + restart
+        (nmfc_engine_set_euclid).  on=False restores the nmf_mu runs."""
+        if self.L.nmfc_engine_set_euclid(self.h, 1 if on else 0, int(stopconv), int(stopfreq)) != 0:
+            raise ValueError(f"nmfc_engine_set_euclid failed: {_lib.last_error()}")
+        self._euclid = dict(stopconv=int(stopconv), stopfreq=int(stopfreq)) if on else None
 
     def residuals(self) -> np.ndarray:
         """dnorm of every shard job of the last run, which must have had residuals enabled (nmfc_engine_residuals)."""
@@ -212,14 +225,15 @@ class Engine:
             want_factors: bool = False, want_counts: bool = True, counts_device_ptr: int | None = None,
             check_every: int = 4, min_init: int = 0, max_init: int = 1, verbose: bool = False,
             TolX: float = 1e-4, TolFun: float = 1e-4, init_stream: int = INIT_LIBNMF, want_h: bool = False,
-            want_residuals: bool = False, want_best: bool = False) -> SweepResult:
+            want_residuals: bool = False, want_best: bool = False, euclid: dict | None = None) -> SweepResult:
         """One sweep of the (k, restart) job grid (or its shard [job_begin, job_end)).  want_factors: final W and
         H of every job; want_h: final H only (the C3-sized checks: W of 1800 jobs is 1.7 GB of host memory).
         want_residuals: SweepResult.dnorm, every job's ||A - W H||_F / sqrt(m n), from one batched pass on the device
         (no factor download); want_best (implies want_residuals): SweepResult.best, per rank of the shard the restart
         with the smallest dnorm and its W, H -- the only factors that leave the device.  Both are enabled for this
         call only; the engine's set_residuals() setting (which, when on, fills dnorm on every run) is restored
-        afterwards."""
+        afterwards.  euclid=dict(stopconv=, stopfreq=): this call runs the BROAD script's Euclidean NMF() (set_euclid)
+        and the engine's set_euclid() setting is restored afterwards; None leaves that setting as it is."""
         ks = [int(k) for k in ks]
         nk = len(ks)
         njobs_all = nk * R
@@ -269,6 +283,9 @@ class Engine:
             if wi.size != sum(m * k for k in jk) or hi.size != sum(k * n for k in jk):
                 raise ValueError("W_init/H_init sizes do not match the job shard")
         ks_arr = np.array(ks, dtype=np.int32)
+        prev_euclid = self._euclid
+        if euclid is not None:   # first: bad arguments raise before any other setting has changed
+            self.set_euclid(True, **euclid)
         prev = self._residuals
         want_residuals = want_residuals or want_best or prev
         if want_residuals != prev:
@@ -280,6 +297,8 @@ class Engine:
         finally:
             if want_residuals != prev:
                 self.set_residuals(prev)
+            if euclid is not None:
+                self.set_euclid(prev_euclid is not None, **(prev_euclid or {}))
         if rc != 0:
             raise RuntimeError(f"nmfc_engine_run failed: {_lib.last_error()}")
         self._last_ks, self._last_nj = ks, nj
