@@ -1617,6 +1617,9 @@ static constexpr int ahtw4_lds() {
 // RULE_EUCLID: euclid_rule_w instead of mu_rule_sel.  That rule has no zero guard, so a padded gene row (gene >= m,
 // all of old, num and den zero) would become 0 * 0 / 0 + eps = NaN and poison W^T W: the epilogue masks by the gene
 // index (the kernel receives m beside ngt) and writes +0.0 there; a real row follows the rule whatever it holds.
+// A real row can therefore turn NaN (a zero column of a caller's W0), and E = W0 (h h^T) would hand that NaN to the
+// other restarts of its 16-column block as 0 x NaN: a block whose W0 holds a non-finite value takes a path of its own
+// in the epilogue, restart by restart, that gives every restart the bits it has alone.
 template <int GTG = GT, int NBUF = GT_NBUF, int NPT = 1, int PR = PANEL, int WC = 4, bool LATE = false, bool KHALF = false,
           int RULE = RULE_MU>
 static __global__ __launch_bounds__(64 * NPT * WC,
@@ -1733,6 +1736,64 @@ void k_ahtw4(int iter, const double* __restrict__ H, long n_pad, const double* _
     const int ra = 16 * mb + (lane & 15);
     const int alc = __shfl(cc.lc0, ra) & (PR - 1);   // tile-local (a restart never straddles a tile)
     const int ak = ((actmask >> ra) & 1) ? __shfl(cc.k, ra) : 0;
+    if constexpr (RULE == RULE_EUCLID) {
+      // E below multiplies every W0 column of its K steps into every row and relies on 0 x finite = 0 outside a row's
+      // own restart.  This rule has no guard, so a restart can hold NaN or Inf (a caller's zero column of W0 gives
+      // 0 / 0), live or stopped, and 0 x NaN would hand it to every restart of the block.  When a K step holds a
+      // non-finite W0, the block is done restart by restart instead, the other restarts' columns of W0 masked to 0.0: the
+      // same K steps in the same order with zeros for zeros, so a finite restart keeps its bits and a non-finite one
+      // gets R's IEEE result.
+      bool nonfin = false;
+#pragma unroll
+      for (int b2 = 0; b2 < TileW4::MB; ++b2) {
+        if (b2 < mb - 1 || b2 > mb + 1 || (aligned && b2 != mb)) continue;   // the blocks E reads
+#pragma unroll
+        for (int nb = 0; nb < TileW4::NB; ++nb)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg)
+            nonfin |= __builtin_amdgcn_class(w0[b2][nb][reg], 0x207);   // NaN or +-Inf
+      }
+      if (__ballot(nonfin) != 0) {   // wave-uniform
+#pragma unroll 1
+        for (int x = 0; x < 16; ++x) {   // the restarts with a column in block mb, by their first column in it
+          const int col = 16 * mb + x;
+          const int st = __builtin_amdgcn_readfirstlane(__shfl(cc.lc0, col)) & (PR - 1);
+          const int kk = __builtin_amdgcn_readfirstlane(__shfl(cc.k, col));
+          if (kk == 0 || (st != col && x != 0) || !((actmask >> col) & 1)) continue;
+          // opaque copies: nothing of this loop is computed ahead of it and held in registers across the tile's hot path
+          // (without them LICM hoists old * num and the row tests of all four registers, and the 64-gene form, which
+          // sits on its 96-VGPR cap, spills into the K loop).  They only steer register allocation;
+          // tests/test_euclid_resources.py compiles this file and fails on a spill, on scratch or on fewer waves per
+          // SIMD than the nmf_mu form has (hipcc of ROCm 7.2, clang 22: 158 / 96 / 48 VGPRs for the 128-, 64-gene and narrow forms).
+          int l4 = lane >> 4;
+          asm volatile("" : "+v"(l4));
+#pragma unroll
+          for (int nb = 0; nb < TileW4::NB; ++nb) {
+            d4 t = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int q = (4 * mb - 4 > 0 ? 4 * mb - 4 : 0); q < (4 * mb + 8 < 4 * TileW4::MB ? 4 * mb + 8 : 4 * TileW4::MB); ++q) {
+              if (4 * q + 3 < st || 4 * q >= st + kk) continue;   // wave-uniform
+              const int ck = 4 * q + l4;                          // the K step's column of this lane
+              const bool own = ck >= st && ck < st + kk;
+              const double sv = (own && alc == st) ? SHw[ra * KMAX + ck - st] : 0.0;
+              const double bv = own ? w0[q >> 2][nb][q & 3] : 0.0;
+              t = __builtin_amdgcn_mfma_f64_16x16x4f64(sv, bv, t, 0, 0, 0);
+            }
+            const int gene = gt * GTG + (GTG / WC) * wc + 16 * nb + (lane & 15);
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+              const int c = 16 * mb + l4 + 4 * reg;
+              if (c < st || c >= st + kk) continue;
+              double old = w0[mb][nb][reg];
+              asm volatile("" : "+v"(old));
+              const double v = gene < tiles.m ? euclid_rule_w(old, tl.acc[mb][nb][reg], t[reg]) : 0.0;
+              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rw, wvoff, woff(mb, reg, nb), 0);
+            }
+          }
+        }
+        continue;
+      }
+    }
     d4 e[TileW4::NB];
 #pragma unroll
     for (int nb = 0; nb < TileW4::NB; ++nb) e[nb] = d4{0.0, 0.0, 0.0, 0.0};

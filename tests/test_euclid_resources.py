@@ -52,3 +52,9 @@ def test_euclid_kernels_resources():
         e, b = one(f"k_ahtw4ILi128ELi2ELi1ELi64ELi4ELb1ELb{kh}ELi1E"), one(f"k_ahtw4ILi128ELi2ELi1ELi64ELi4ELb1ELb{kh}ELi0E")
         assert e["occ"] >= 3 and e["occ"] >= b["occ"], (e, b)
     assert one(HUPD_EUCLID)["occ"] >= one(HUPD_MU)["occ"] >= 4
+    # every form keeps the waves per SIMD of its nmf_mu counterpart: the epilogue's path for a block with a non-finite W0
+    # (k_ahtw4, RULE_EUCLID) holds its loop-invariant values behind opaque copies so that it costs the hot path no
+    # register; a compiler that undoes this shows here as a spill (above) or as lost occupancy
+    for key in AHTW_EUCLID:
+        e, b = one(key), one(key[:-4] + "Li0E")
+        assert e["occ"] >= b["occ"], (key, e, b)

@@ -4,7 +4,9 @@ brunet.NMF, brunet.nmfconsensus(error_function="euclidean")) against the numpy r
 1. values: FIXED T iterations against the long-double literal form, every W and H finite and >= 2^-52 (a NaN anywhere
    is the padded-gene-row bug); 2. the exact H rule on integer data, bit for bit; 3. the membership stop rule job for
    job against the Gram fp64 form; 4. the same bits under every placement (polls, repacks, shards, no narrow tail);
-   5. the Python interface; 6. disabling restores the nmf_mu runs, and bad arguments are refused.
+   5. the Python interface; 6. disabling restores the nmf_mu runs, and bad arguments are refused; 7. a restart that
+   turns NaN (a zero column in its W0) stays alone: its neighbours in the batch and the next run on the engine keep
+   their bits.  (Every element against a derived bound on wide-range data: tests/test_gpu_widerange.py.)
 Lines starting "EUC|" print each figure before it is asserted.
 """
 import contextlib
@@ -120,6 +122,38 @@ def test_exact_h_rule(m, n, k):
         told_apart += int((want != (H0[j] * num) / den + er.EPS).sum()) + int((want != H0[j] * (num / den)).sum())
         assert np.all(np.isfinite(r.W[j])) and r.W[j].min() >= er.EPS
     # multiply-then-divide, or no eps, gives other bits on this data: the comparison can tell the orders apart
+    assert told_apart > 0
+
+
+@pytest.mark.parametrize("m,n,k", [(130, 17, 3), (1100, 72, 5)])
+def test_exact_h_rule_sees_a_fused_add(m, n, k):
+    """The same with A in 0, 16, .., 112: most products H0 * q then lie above 2, where eps is half a unit in the last place
+    and below, so the multiply and the add rounded as one (an FMA, what the compiler makes of the rule without its
+    contract(off)) gives other bits than two roundings on part of the entries.  On test_exact_h_rule's own data the
+    products lie below 2, where eps is a whole number of units and the two forms agree."""
+    from nmfconsensus_amd.nmf import Engine
+    rng = np.random.default_rng(m * 1000 + n + 1)
+    A = np.asfortranarray(16.0 * rng.integers(0, 8, size=(m, n)).astype(np.float64))
+    R = 2
+    W0 = [np.asfortranarray(rng.integers(1, 5, size=(m, k)).astype(np.float64)) for _ in range(R)]
+    H0 = [np.asfortranarray(rng.integers(1, 5, size=(k, n)).astype(np.float64)) for _ in range(R)]
+    with Engine(A) as eng:
+        r = eng.run([k], R, maxiter=1, stop_rule=FIXED, W_init=W0, H_init=H0, want_factors=True, want_counts=False,
+                    euclid=DEFAULT)
+    told_apart = 0
+    for j in range(R):
+        num = W0[j].T @ A
+        den = (W0[j].T @ W0[j]) @ H0[j]
+        assert num.max() < 2.0 ** 53 and den.max() < 2.0 ** 53
+        q = num / den
+        want = H0[j] * q + er.EPS
+        # H0 (3 bits) times q (53 bits) plus eps is exact in a 64-bit significand (the x87 long double that
+        # tests/widerange.py also requires): one rounding to fp64 is then the FMA
+        assert np.finfo(LD).eps <= 2.0 ** -63
+        fused = (H0[j].astype(LD) * q.astype(LD) + LD(er.EPS)).astype(np.float64)
+        told_apart += int((want != fused).sum())
+        assert np.array_equal(r.H[j], want), (j, int((r.H[j] != want).sum()), int((r.H[j] == fused).sum()))
+    print(f"EUC|exact H rule, A times 16|{m}x{n} k={k}|entries where a fused add gives other bits: {told_apart} of {R * k * n}")
     assert told_apart > 0
 
 
@@ -361,3 +395,145 @@ def test_bad_arguments():
         # a refused setting leaves the mode off: this is an nmf_mu run on the small-shape path
         eng.run([2], 1, maxiter=3, stop_rule=FIXED, want_counts=False)
         assert eng.last_run_info()["small"] == 1
+
+
+# ---- 7. a poisoned restart stays alone --------------------------------------------------------------------------------
+# The rule has no zero guard (nmfc.h: "IEEE results as R's"): a restart whose W0 has an all-zero column divides 0 by 0
+# in the first H update.  R gives that restart NaN and nothing else; so must a batch that holds it, and so must the next
+# run on the same engine.  The A h^T epilogue has a path of its own for a 16-column block that holds a non-finite W0,
+# compiled into all five RULE_EUCLID forms, so the batches below reach each form:
+#   narrow            200 x 60, k = 3, four restarts: twelve columns in one block, the 16-column narrow form;
+#   200x60-tile*      k = 5, seven restarts, NMFC_NARROW=0: blocks of three restarts, [0 1 2] [3 4 5] [6] in one panel;
+#                     the poisoned restart 4 is the middle one of block 1, with finite neighbours in its own block and in
+#                     the blocks before and after it; the 64- and the 128-gene tile, n_pad - n = 4: no K-half skip;
+#   1100x72-tile*     the same batch with n_pad - n = 24: the K-half skip, and nine gene tiles of 128.
+# name: (m, n, k, R, the poisoned job, seed, environment, the A h^T form of last_run_info that must have run)
+_WIDE = {"NMFC_NARROW": "0"}
+POISON_CASES = {
+    "narrow": (200, 60, 3, 4, 1, 67, {}, "ahtw_narrow"),
+    "200x60-tile64": (200, 60, 5, 7, 4, 67, dict(_WIDE, NMFC_AHTW_TILE="64"), "ahtw_64"),
+    "200x60-tile128": (200, 60, 5, 7, 4, 67, dict(_WIDE, NMFC_AHTW_TILE="128"), "ahtw_128"),
+    "1100x72-tile64": (1100, 72, 5, 7, 4, 67, dict(_WIDE, NMFC_AHTW_TILE="64"), "ahtw_64"),
+    "1100x72-tile128": (1100, 72, 5, 7, 4, 67, dict(_WIDE, NMFC_AHTW_TILE="128"), "ahtw_128"),
+}
+AHTW_FORMS = ("ahtw_narrow", "ahtw_64", "ahtw_128")
+
+
+@functools.lru_cache(maxsize=None)
+def poison_inits(name):
+    """(W0 list, H0 list) of the healthy batch, and of the same batch with column 0 of the poisoned job's W0 set to 0.0."""
+    m, n, k, R, bad, seed, _, _ = POISON_CASES[name]
+    W0, H0 = zip(*(er.r_init(seed + i, m, n, k) for i in range(1, R + 1)))
+    Wp = [w.copy(order="F") for w in W0]
+    Wp[bad][:, 0] = 0.0
+    return (list(W0), list(H0)), (Wp, list(H0))
+
+
+def poison_run(eng, name, inits, **kw):
+    """One batch of the case; asserts that every A h^T launch of the run took the form the case is there for."""
+    _, _, k, R, _, _, _, form = POISON_CASES[name]
+    r = eng.run([k], R, W_init=inits[0], H_init=inits[1], want_factors=True, euclid=kw.pop("euclid", DEFAULT), **kw)
+    info = eng.last_run_info()
+    assert info["small"] == 0 and info[form] >= r.iters.max() and all(info[f] == 0 for f in AHTW_FORMS if f != form), info
+    return r
+
+
+def assert_others_same(name, r, base, what):
+    """Every job but the poisoned one: iteration count, early flag, labels, W and H bit-identical to the healthy batch."""
+    R, bad = POISON_CASES[name][3], POISON_CASES[name][4]
+    for j in range(R):
+        if j == bad:
+            continue
+        assert r.iters[j] == base.iters[j] and r.stopped_early[j] == base.stopped_early[j], (what, j)
+        assert np.array_equal(r.labels[j], base.labels[j]), (what, j)
+        assert np.array_equal(r.W[j], base.W[j]) and np.array_equal(r.H[j], base.H[j]), \
+            (what, j, int(np.isnan(r.W[j]).sum()), int(np.isnan(r.H[j]).sum()))
+
+
+@pytest.mark.parametrize("name", list(POISON_CASES))
+def test_poisoned_restart_fixed(name):
+    """FIXED T = 1, 2, 3, with the residual pass on: the other jobs keep the healthy batch's bits (W, H, labels,
+    dnorm); the poisoned job has the NaN pattern of the fp64 Gram form (T = 1: row 0 of H and all of W; from T = 2:
+    everything), its finite entries at T = 1 within widerange.bound_u of that form, labels all 1 and dnorm NaN."""
+    import widerange as wr
+    from nmfconsensus_amd.nmf import Engine
+    m, n, k, R, bad, _, env, _ = POISON_CASES[name]
+    good, pois = poison_inits(name)
+    V = er.planted(m, n)
+    others = [j for j in range(R) if j != bad]
+    with environ(env), Engine(V) as eng:
+        for T in (1, 2, 3):
+            base = poison_run(eng, name, good, maxiter=T, stop_rule=FIXED, want_residuals=True)
+            r = poison_run(eng, name, pois, maxiter=T, stop_rule=FIXED, want_residuals=True)
+            assert np.all(r.iters == T) and not r.stopped_early.any()
+            assert np.all(np.isfinite(base.dnorm)) and all(np.isfinite(x).all() for x in base.W + base.H)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                Wg, Hg, _, _ = er.run(V, pois[0][bad], pois[1][bad], T, form="gram", fixed=True)
+            W, H = r.W[bad], r.H[bad]
+            print(f"EUC|poison|{name}|FIXED T={T}|job {bad}: NaN in W {int(np.isnan(W).sum())} of {W.size}, in H "
+                  f"{int(np.isnan(H).sum())} of {H.size}|other jobs: NaN in W "
+                  f"{sum(int(np.isnan(r.W[j]).sum()) for j in others)}, in H {sum(int(np.isnan(r.H[j]).sum()) for j in others)}")
+            assert np.array_equal(np.isnan(W), np.isnan(Wg)) and np.array_equal(np.isnan(H), np.isnan(Hg)), T
+            assert not np.isinf(W).any() and not np.isinf(H).any()
+            if T == 1:
+                assert np.isnan(W).all() and np.isnan(H[0]).all() and np.isfinite(H[1:]).all()
+                bh, _ = wr.bound_u(m, n, k, 1)
+                eh = wr.cw_check(H[1:], Hg[1:], bh, "the finite rows of the poisoned job's H")
+                print(f"EUC|poison|{name}|FIXED T=1|finite rows of H {eh:.0f} u of {bh}")
+            else:
+                assert np.isnan(W).all() and np.isnan(H).all()
+            assert np.all(r.labels[bad] == 1)
+            assert_others_same(name, r, base, f"FIXED T={T}")
+            assert np.isnan(r.dnorm[bad])
+            for j in others:
+                assert r.dnorm[j] == base.dnorm[j], (T, j, r.dnorm[j], base.dnorm[j])
+
+
+@pytest.mark.parametrize("check_every", [4, 1])
+@pytest.mark.parametrize("name", list(POISON_CASES))
+def test_poisoned_restart_membership_rule(name, check_every):
+    """stopconv = 2, stopfreq = 1, maxiter = 50: the poisoned job's class never leaves 1 and the first check counts as
+    a change, so it stops at t = 3; its columns then sit dead and full of NaN beside the other jobs, which run on
+    and end as in the healthy batch."""
+    from nmfconsensus_amd.nmf import Engine
+    m, n, _, _, bad, _, env, _ = POISON_CASES[name]
+    good, pois = poison_inits(name)
+    rule = dict(stopconv=2, stopfreq=1)
+    with environ(env), Engine(er.planted(m, n)) as eng:
+        base = poison_run(eng, name, good, maxiter=50, euclid=rule, check_every=check_every)
+        r = poison_run(eng, name, pois, maxiter=50, euclid=rule, check_every=check_every)
+    print(f"EUC|poison|{name}|membership check_every={check_every}|iters {r.iters.tolist()} (healthy {base.iters.tolist()})|"
+          f"early {r.stopped_early.tolist()}")
+    assert r.iters[bad] == 3 and r.stopped_early[bad] == 1 and np.all(r.labels[bad] == 1)
+    assert base.iters.max() > 3 + check_every     # the other jobs ran on beside the dead columns
+    assert all(np.isfinite(x).all() for x in base.W + base.H)
+    assert_others_same(name, r, base, f"membership rule, check_every={check_every}")
+
+
+@pytest.mark.parametrize("name", list(POISON_CASES))
+def test_engine_clean_after_poisoned_runs(name):
+    """After the poisoned runs a healthy run on the same engine gives the bits of a fresh engine: nothing non-finite
+    stays behind in padding, dead columns or the archive.  The same batch, and one of other ranks laid over them."""
+    from nmfconsensus_amd.nmf import Engine
+    m, n, _, _, _, seed, env, _ = POISON_CASES[name]
+    good, pois = poison_inits(name)
+    V = er.planted(m, n)
+
+    def healthy(eng):
+        return (poison_run(eng, name, good, maxiter=2, stop_rule=FIXED, want_residuals=True),
+                eng.run([2, 5], 3, maxiter=2, seed=seed, stop_rule=FIXED, init_stream=INIT_R_RUNIF, want_factors=True,
+                        want_residuals=True, euclid=DEFAULT))
+
+    with environ(env), Engine(V) as eng:
+        fresh = healthy(eng)
+    with environ(env), Engine(V) as eng:
+        for T in (1, 2, 3):
+            poison_run(eng, name, pois, maxiter=T, stop_rule=FIXED, want_residuals=True)
+        poison_run(eng, name, pois, maxiter=50, euclid=dict(stopconv=2, stopfreq=1))
+        after = healthy(eng)
+    for a, f in zip(after, fresh):
+        assert np.array_equal(a.iters, f.iters) and np.array_equal(a.labels, f.labels)
+        assert np.array_equal(a.dnorm, f.dnorm) and np.all(np.isfinite(a.dnorm))
+        assert np.array_equal(a.counts, f.counts)
+        for j in range(len(a.W)):
+            assert np.array_equal(a.W[j], f.W[j]) and np.array_equal(a.H[j], f.H[j]), j

@@ -13,6 +13,9 @@ ARGMAX, first minimum under R_ORDER, ties included: the all-zero sample column g
 runs T = 40 against the fp64 oracle: identical zero pattern, relfro < 1e-9.  calculateNorm, the one place with a
 subtraction, is held to its elementwise backward bound.  The KL kernels also run at the corners of the domain they admit
 (widerange.CORNER_*: A at 2^64 or 2^-200, caller factors at 2^+-59 alternating inside every restart group).
+The Euclidean NMF() rule (Engine.run(euclid=): k_hupdate and the five k_ahtw4 forms of RULE_EUCLID) runs on a wide case of
+its own whose products lie on both sides of its constant 2^-52, under the same bound; where a factor or a row or column
+of A is zero the result is exactly 2^-52 (test_euclid_sweep).
 
 Every test prints the worst error in u = 2^-53 beside its bound (lines starting "WR|").
 """
@@ -145,6 +148,102 @@ def test_solo_batches(case):
     run next to a k_small_mu block."""
     m, n, ks, R, env = case
     engine_batch("solo-batch" + ("+k9" if 9 in ks else ""), m, n, ks, R, env, small=1)
+
+
+# ---- the Euclidean NMF() rule: k_hupdate and the five k_ahtw4 forms of RULE_EUCLID ---------------------------------------
+
+EPS = wr.EUCLID_EPS
+_euclid_runs = {}
+
+
+def euclid_form(info, n):
+    """The A h^T forms a run launched, from last_run_info: "narrow", "64" / "128", "-kskip" where n_pad - n >= 8."""
+    skip = "-kskip" if wr.euclid_kskip(n) else ""
+    return ({"narrow"} if info["ahtw_narrow"] else set()) | ({"64" + skip} if info["ahtw_64"] else set()) | \
+           ({"128" + skip} if info["ahtw_128"] else set())
+
+
+def euclid_batch(index):
+    """Batch `index` of widerange.EUCLID_BATCHES through Engine.run(euclid=) under its environment, T = 1 and 2, both
+    label rules: {T: (ARGMAX run, R_ORDER run)} and the set of A h^T forms launched.  Run once, kept for the
+    comparisons between batches."""
+    if index in _euclid_runs:
+        return _euclid_runs[index]
+    from nmfconsensus_amd.nmf import Engine
+    m, n, ks, R, env = wr.EUCLID_BATCHES[index]
+    nk = len(ks)
+    jobs = [(ks[j % nk], j // nk) for j in range(nk * R)]
+    W0 = [wr.case("euclid", m, n, k, q)[1] for k, q in jobs]
+    H0 = [wr.case("euclid", m, n, k, q)[2] for k, q in jobs]
+    out, forms = {}, set()
+    with environ(env), Engine(wr.wide_A(m, n, wr.SEED, "euclid")) as eng:
+        for T in (1, 2):
+            runs = []
+            for rule in (ARGMAX, R_ORDER):
+                r = eng.run(list(ks), R, maxiter=T, stop_rule=FIXED, label_rule=rule, W_init=W0, H_init=H0,
+                            want_factors=True, euclid=dict(stopconv=40, stopfreq=10))
+                info = eng.last_run_info()
+                assert info["small"] == 0
+                assert info["ahtw_narrow"] + info["ahtw_64"] + info["ahtw_128"] == T, info
+                forms |= euclid_form(info, n)
+                assert np.all(r.iters == T) and not r.stopped_early.any()
+                runs.append(r)
+            out[T] = tuple(runs)
+    _euclid_runs[index] = (out, forms)
+    return _euclid_runs[index]
+
+
+def euclid_id(index):
+    m, n, ks, _, env = wr.EUCLID_BATCHES[index]
+    return batch_id((m, n, ks)) + "".join(f"-{k[5:].lower()}{v}" for k, v in sorted(env.items()))
+
+
+@pytest.mark.parametrize("index", range(len(wr.EUCLID_BATCHES)), ids=euclid_id)
+def test_euclid_sweep(index):
+    """Engine.run(euclid=) on the wide Euclidean case: every element of W and H of every job within bound_u of the
+    long-double Gram form; exactly eps where W0 or H0 is zero (T = 1) and on the all-zero row and column of A; labels
+    from the run's own H; the same bits under both label rules and under the environments of EUCLID_SAME_BITS."""
+    m, n, ks, R, env = wr.EUCLID_BATCHES[index]
+    nk = len(ks)
+    jobs = [(ks[j % nk], j // nk) for j in range(nk * R)]
+    for k in ks:
+        wr.prefetch("euclid", m, n, k, range(R))
+    runs, forms = euclid_batch(index)
+    assert wr.EUCLID_FORMS[index] in forms, (forms, "the batch no longer takes the form it is here for")
+    worst = Worst("euclid-" + "+".join(sorted(forms)))
+    of_k = [list(range(i, nk * R, nk)) for i in range(nk)]
+    for T in (1, 2):
+        a, b = runs[T]
+        for j, (k, q) in enumerate(jobs):
+            assert np.array_equal(a.W[j], b.W[j]) and np.array_equal(a.H[j], b.H[j]), j
+            worst.check("euclid", m, n, k, q, T, a.W[j], a.H[j])
+            _, W0, H0 = wr.case("euclid", m, n, k, q)
+            assert np.all(a.W[j][5 % m, :] == EPS) and np.all(a.H[j][:, 3 % n] == EPS), (j, T)
+            if T == 1:
+                assert (W0 == 0).any() and (H0 == 0).any()
+                assert np.all(a.W[j][W0 == 0] == EPS) and np.all(a.H[j][H0 == 0] == EPS), j
+        # the all-zero column of A holds eps in every row: a tie, so the first row under both rules
+        check_labels(a, of_k, R, n, np.argmax)
+        check_labels(b, of_k, R, n, np.argmin)
+        assert np.all(a.labels[:, 3 % n] == 1) and np.all(b.labels[:, 3 % n] == 1)
+    worst.report()
+    for x, y in wr.EUCLID_SAME_BITS:
+        if index in (x, y):
+            other, _ = euclid_batch(x + y - index)
+            for T in (1, 2):
+                for j in range(nk * R):
+                    assert np.array_equal(runs[T][0].W[j], other[T][0].W[j]), (x, y, T, j)
+                    assert np.array_equal(runs[T][0].H[j], other[T][0].H[j]), (x, y, T, j)
+
+
+def test_euclid_sweep_reaches_every_form():
+    """The union of the forms the batches of EUCLID_BATCHES launched: the narrow form and the 64- and the 128-gene tile,
+    each with and without the K-half skip."""
+    seen = set()
+    for index in range(len(wr.EUCLID_BATCHES)):
+        seen |= euclid_batch(index)[1]
+    print(f"WR|euclid|forms launched: {sorted(seen)}")
+    assert seen >= wr.EUCLID_ALL_FORMS, seen
 
 
 # ---- the single-restart entries ---------------------------------------------------------------------------------------

@@ -5,7 +5,11 @@ against the long-double reference at T = 1 and T = 2 (4..116 u against bounds of
 make the check worth running: a fifth of the rows of W and of the columns of H below what the relative Frobenius bar of
 1e-9 can see, MU denominators on both sides of 1e-9 on the H side and on the W side, no value near the underflow or
 overflow limits (so every zero is structural), and for KL brunet.hip's admitted domain.  A numpy restatement of the MU
-update without DIV_BY_ZERO_AVOIDANCE, and one with the constant doubled, fail the check by many orders."""
+update without DIV_BY_ZERO_AVOIDANCE, and one with the constant doubled, fail the check by many orders.
+The Euclidean NMF() cases (widerange.EUCLID_BATCHES): positive denominators and normal intermediates, the rule's products
+on both sides of 2^-52, the elements that are exactly 2^-52, and the fp64 Gram form of tests/euclid_ref.py inside the
+bound (4..45 u against bounds of 207..256 980 u); eps added twice or before the divide, or the MU rule's 1e-9 in the
+denominator, miss it by 1e15 u and more."""
 import numpy as np
 import pytest
 
@@ -28,7 +32,7 @@ def test_bound_recursion_values():
     assert (bh, bw) == (3 * 6132 + 2 * 2013 + 2013, 3 * (3 * 6132 + 2 * 2013 + 2013) + 2 * 6132 + 93)
     assert 80000 < bw < 90000
     # the largest bound any test uses still sits far below the 1e-9 of the norm-wise bar
-    assert max(max(wr.bound_u(m, n, k, 2)) for m, n, k in MU + KL) * wr.U < 1e-10
+    assert max(max(wr.bound_u(m, n, k, 2)) for m, n, k in MU + KL + wr.euclid_shapes()) * wr.U < 1e-10
 
 
 def test_cw_check_rejects():
@@ -172,6 +176,117 @@ def test_constant_sensitivity(m, n, k):
         W, H = mu_fp64(Au, Wu, Hu, 24, eps)
         print(f"constant {name} on uniform {m}x{n} k={k}, T=24: relfro W {relfro(W, Wt):.2e} H {relfro(H, Ht):.2e} "
               f"(the bar is 1e-9)")
+
+
+# ---- the Euclidean NMF() rule (widerange.EUCLID_BATCHES) ----------------------------------------------------------------
+
+EUC = wr.euclid_shapes()
+EUC_R = {(m, n, k): max(R for mm, nn, ks, R, _ in wr.EUCLID_BATCHES if (mm, nn) == (m, n) and k in ks) for m, n, k in EUC}
+
+
+def euclid_fp64(A, W0, H0, T):
+    """T updates of the fp64 Gram form of tests/euclid_ref.py."""
+    import euclid_ref as er
+    W, H = np.array(W0), np.array(H0)
+    for _ in range(T):
+        W, H = er._update(np.asarray(A), W, H, np.float64(er.EPS), "gram")
+    return W, H
+
+
+def euclid_exact_eps(m, n, W0, H0, T):
+    """(mask of W, mask of H) of the elements the rule leaves at exactly eps after T updates: the all-zero row 5 % m of
+    A (a row of W), its all-zero column 3 % n (a column of H) and, after the first update, every zero of W0 and H0."""
+    zw, zh = (W0 == 0) & (T == 1), (H0 == 0) & (T == 1)
+    zw[5 % m, :] = True
+    zh[:, 3 % n] = True
+    return zw, zh
+
+
+def test_euclid_recipe():
+    m, n, k = 1100, 72, 7
+    A, W0, H0 = wr.case("euclid", m, n, k)
+    assert A.flags["F_CONTIGUOUS"] and A.shape == (m, n) and W0.shape == (m, k) and H0.shape == (k, n)
+    assert np.all(A[5 % m, :] == 0) and np.all(A[:, 3 % n] == 0) and 0.25 < np.mean(A == 0) < 0.40
+    # the same draws as the MU matrix at another scale
+    assert np.allclose(A, wr.case("mu", m, n, k)[0] * (wr.ALPHA["euclid"] / wr.ALPHA["mu"]), rtol=1e-14, atol=0)
+    W3 = wr.case("euclid", m, n, k, 3)[1]
+    assert wr.case("euclid", m, n, k, 3)[0] is A
+    assert np.median(W3[W3 > 0]) < np.median(W0[W0 > 0]) * 2.0 ** -16
+    assert wr.EUCLID_EPS == 2.0 ** -52 and wr.EUCLID_EPS == np.finfo(np.float64).eps
+    # every RULE_EUCLID form of the A h^T kernel has a batch that is there for it
+    assert set(wr.EUCLID_FORMS) == wr.EUCLID_ALL_FORMS
+    for a, b in wr.EUCLID_SAME_BITS:
+        assert wr.EUCLID_BATCHES[a][:4] == wr.EUCLID_BATCHES[b][:4] and wr.EUCLID_BATCHES[a][4] != wr.EUCLID_BATCHES[b][4]
+
+
+@pytest.mark.parametrize("m,n,k", EUC, ids=ids(EUC))
+def test_euclid_case(m, n, k):
+    """(a) denominators positive, intermediates zero or normal; (b) eps decides on both sides; (c) the exact-eps sets;
+    (d) the fp64 Gram form inside the bound.  Job 0 for all four; the scaled jobs of the batch for (a), (c) and (d)."""
+    tiny, huge = np.finfo(np.float64).tiny, np.finfo(np.float64).max
+    wr.prefetch("euclid", m, n, k, range(EUC_R[(m, n, k)]))
+    for job in range(EUC_R[(m, n, k)]):
+        A, W0, H0 = wr.case("euclid", m, n, k, job)
+        for X in (W0, H0):
+            assert 0.03 < np.mean(X == 0) < 0.18   # about 10 %
+            assert not (X == 0).all(axis=0).any() and not (X == 0).all(axis=1).any()
+        # (a)
+        c = wr.measure_euclid(A, W0, H0)
+        print(f"euclid {m}x{n} k={k} job {job}: " + " ".join(f"{a}={b:.3g}" for a, b in c.items()))
+        assert c["Hden_min"] > 0 and c["Wden_min"] > 0, c
+        assert tiny <= c["min"] and c["max"] <= huge, c
+        # (b)
+        if job == 0:
+            for side in "HW":
+                assert c[f"{side}lo"] >= 0.05 and c[f"{side}hi"] >= 0.25, (side, c)
+        # (c)
+        assert (W0 == 0).any() and (H0 == 0).any()
+        ref = wr.reference("euclid", m, n, k, job)
+        for T in (1, 2):
+            Wr, Hr = ref[T]
+            zw, zh = euclid_exact_eps(m, n, W0, H0, T)
+            assert zw[5 % m, :].all() and zh[:, 3 % n].all()
+            assert np.all(Wr[zw] == wr.LD(wr.EUCLID_EPS)) and np.all(Hr[zh] == wr.LD(wr.EUCLID_EPS))
+            assert np.all(Wr >= wr.LD(wr.EUCLID_EPS)) and np.all(Hr >= wr.LD(wr.EUCLID_EPS))
+            # (d)
+            W, H = euclid_fp64(A, W0, H0, T)
+            bh, bw = wr.bound_u(m, n, k, T)
+            eh = wr.cw_check(H, Hr, bh, f"fp64 Gram form H {m}x{n} k={k} job {job} T={T}")
+            ew = wr.cw_check(W, Wr, bw, f"fp64 Gram form W {m}x{n} k={k} job {job} T={T}")
+            print(f"  fp64 Gram form job {job} T={T}: H {eh:.0f} u of {bh}, W {ew:.0f} u of {bw}")
+            assert np.all(W[zw] == wr.EUCLID_EPS) and np.all(H[zh] == wr.EUCLID_EPS)
+
+
+def euclid_mutant(A, W0, H0, which):
+    """One fp64 update with the rule got wrong in the ways a kernel could get it wrong."""
+    eps = wr.EUCLID_EPS
+    num, den = W0.T @ A, (W0.T @ W0) @ H0
+    H = H0 * (num / (den + 1e-9)) + eps if which == "mu-constant" else H0 * (num / den) + eps
+    num, den = A @ H.T, W0 @ (H @ H.T)
+    if which == "eps-twice":
+        W = (W0 * num) / den + eps + eps
+    elif which == "eps-before-divide":
+        W = (W0 * num + eps) / den
+    else:
+        W = (W0 * num) / den + eps
+    return W, H
+
+
+@pytest.mark.parametrize("m,n,k", [(97, 33, 5), (200, 60, 4), (1100, 72, 7)])
+def test_euclid_constant_sensitivity(m, n, k):
+    """eps added twice or before the divide (W), or the MU rule's 1e-9 in the H denominator: each misses the bound at
+    T = 1 on the wide case by orders; the restatement without a mutation passes."""
+    A, W0, H0 = wr.case("euclid", m, n, k)
+    Wr, Hr = wr.reference("euclid", m, n, k)[1]
+    bh, bw = wr.bound_u(m, n, k, 1)
+    W, H = euclid_mutant(A, W0, H0, None)
+    wr.cw_check(H, Hr, bh, "restatement H"), wr.cw_check(W, Wr, bw, "restatement W")
+    for which, side in (("eps-twice", "W"), ("eps-before-divide", "W"), ("mu-constant", "H")):
+        W, H = euclid_mutant(A, W0, H0, which)
+        _, err = wr.cw_error(H, Hr) if side == "H" else wr.cw_error(W, Wr)
+        bound = bh if side == "H" else bw
+        print(f"euclid {which} on wide {m}x{n} k={k}: {side} off by {err:.3g} u (bound {bound})")
+        assert err > 1e6 * bound
 
 
 # ---- the KL kernels at the corners of their domain (widerange.CORNER_*) ------------------------------------------------

@@ -51,7 +51,23 @@ Where the recipe had to move to meet the conditions test_widerange_reference.py 
   * the scales are drawn stratified (_log_uniform), so five or eight of them still cover the decades.
   * MU_W0_MK: above m k = 16384, W0 is scaled down to keep the H-side denominator on both sides of 1e-9.
   * KL_W0_SCALE: the KL factors times 2^20, to stay inside [2^-60, 2^60] under the batch scaling of 2^-32.
-  * RESEED: ten (shape, k) cases take a later init seed, where the draw left one side's denominators one-sided.
+  * RESEED: ten MU (shape, k) cases take a later init seed, where the draw left one side's denominators one-sided.
+
+The third kind, "euclid": the BROAD script's Euclidean NMF() in the Gram form the engine runs (ref_euclid),
+H <- H * ((W^T A) / ((W^T W) H)) + eps, then W <- (W * (A H^T)) / (W (H H^T)) + eps with the new H, eps = 2^-52, no guard
+and no clamp.  The same recursion bounds it: H is divide, multiply, add and W is multiply, divide, add, three roundings
+each and inside the "+ 8"; nothing is subtracted, and adding the positive eps never raises a relative error.
+The data is wide_A with a scale of its own (ALPHA["euclid"] = 1e-26) and wide_init with W0 times 2^-34
+(EUCLID_W0_SCALE) and about 10 % exact zeros in W0 and in H0: the rule's products old * q then lie on both sides of eps
+(test_widerange_reference.py asserts the shares), so an eps added twice, added before the divide or replaced by
+another constant decides a third of the values.  A zero of W0 or H0, the all-zero row of A (a row of W) and the
+all-zero column of A (a column of H) give exactly eps.  No row or column of W0 and no row or column of H0 is left
+entirely zero (a zero mask that would make one gives up one entry).  The rule has no guard, so a denominator of 0 means
+NaN: an all-zero row of W0 makes W (H H^T) zero in that row, an all-zero column of W0 makes a row of W^T W and with it
+a row of (W^T W) H zero, and an all-zero column of H0 makes that column of (W^T W) H zero; the last is the one the
+first recipe did not name.  An all-zero row of H0 harms no denominator (the row becomes eps); it is kept out with the
+others so that every row of H0 takes part in the first update.  RESEED: 3001 x 150, k = 2 takes the init seed after
+next, where only 15 of its 300 elements of H (exactly the 5 % asked for) had a product below eps / 8; now 22.
 
 The KL corner cases (CORNER_*, below) are a second recipe: A and the caller factors at the ends of what
 nmfc_brunet_create and nmfc_brunet_run admit.  The same reference and the same bound apply: there is no subtraction, so
@@ -71,7 +87,11 @@ KL_EPS = 2.220446049250313e-16      # .Machine$double.eps, brunet.hip EPS
 
 # global scale of A per update rule (conditions of test_widerange_reference.py: MU puts the W-side denominators on
 # both sides of 1e-9; KL keeps A <= 2^64 and sum(A) <= 2^100)
-ALPHA = {"mu": 10.0 ** -9.5, "kl": 1.0}
+ALPHA = {"mu": 10.0 ** -9.5, "kl": 1.0, "euclid": 1e-26}
+EUCLID_EPS = 2.0 ** -52             # .Machine$double.eps, nmfc_kernels.hpp R_EPS: the constant the Euclidean rule adds
+# Euclid: with A at 1e-26 and W0 at 2^-34 the products H0 * q and (W0 * num) / den of the first update lie on both
+# sides of 2^-52 for every shape of EUCLID_BATCHES
+EUCLID_W0_SCALE = 2.0 ** -34
 # c_j = 10^U(-COL_DECADES, COL_DECADES): the columns of H scale with c_j (KL: with nothing else), and 6 decades in all
 # cannot put a fifth of them 9 decades below the largest
 COL_DECADES = 6.0
@@ -145,6 +165,16 @@ def wide_init(m, n, k, seed, kind="mu", job=0):
         H0[zh] = 0.0
         if k >= 3:
             H0[1, :] = 0.0
+    elif kind == "euclid":
+        # no row or column left entirely zero: the rule has no guard, and a zero denominator would make NaN
+        for z in (zw, zh):
+            for i in np.flatnonzero(z.all(axis=1)):
+                z[i, i % z.shape[1]] = False
+            for j in np.flatnonzero(z.all(axis=0)):
+                z[j % z.shape[0], j] = False
+        W0 *= EUCLID_W0_SCALE
+        W0[zw] = 0.0
+        H0[zh] = 0.0
     else:
         W0 *= KL_W0_SCALE
     W0 *= 2.0 ** (-8 * (job % 5))
@@ -191,8 +221,37 @@ def ref_kl(A, W0, H0, T):
     return W, H
 
 
+def ref_euclid(A, W0, H0, T, trace=None):
+    """The Euclidean NMF() update in the Gram form, in long double: H <- H * ((W^T A) / ((W^T W) H)) + eps, then
+    W <- (W * (A H^T)) / (W (H H^T)) + eps with the new H; eps = 2^-52, no guard, no clamp.  trace: a list that receives,
+    per iteration, a dict of every intermediate of both sides (numerator, Gram matrix, denominator, quotient, product;
+    for H the product is the old * q the eps is added to, for W that is the quotient)."""
+    A, W, H = (np.asarray(x, dtype=LD) for x in (A, W0, H0))
+    e = LD(EUCLID_EPS)
+    for _ in range(T):
+        hnum, hgram = W.T @ A, W.T @ W
+        hden = hgram @ H
+        hq = hnum / hden
+        hp = H * hq
+        H = hp + e
+        wnum, wgram = A @ H.T, H @ H.T
+        wden = W @ wgram
+        wp = W * wnum
+        wq = wp / wden
+        W = wq + e
+        if trace is not None:
+            trace.append(dict(Hnum=hnum, Hgram=hgram, Hden=hden, Hquot=hq, Hprod=hp,
+                              Wnum=wnum, Wgram=wgram, Wden=wden, Wprod=wp, Wquot=wq))
+    return W, H
+
+
+REF = {"mu": ref_mu, "kl": ref_kl, "euclid": ref_euclid}
+
+
 def bound_u(m, n, k, T):
-    """(bound for H, bound for W) after T updates, in units of u = 2^-53: the recursion of the module docstring."""
+    """(bound for H, bound for W) after T updates, in units of u = 2^-53: the recursion of the module docstring.  It
+    holds for the MU, the KL and the Euclidean update alike: none of them subtracts, each elementwise rule is three
+    roundings, and the constant each adds is positive."""
     dH = dW = 0
     for _ in range(T):
         dH = 3 * dW + 2 * dH + (2 * m + k + 8)
@@ -270,6 +329,37 @@ def kl_shapes():
     return sorted({(m, n, k) for m, n, ks in KL_SHAPES for k in ks})
 
 
+# ---- the Euclidean NMF() rule (test_gpu_widerange.py::test_euclid_sweep) ----------------------------------------------
+# Engine.run(euclid=) batches (m, n, ks, R, environment), the smallest shapes that reach every RULE_EUCLID instantiation
+# of k_ahtw4: the 16-column narrow form, and the 64- and the 128-gene tile, each with and without the K-half skip (taken
+# when n_pad - n >= 8, n_pad = n rounded up to 32).  200 x 60: n_pad - n = 4 and a ragged last gene tile; 1100 x 72:
+# n_pad - n = 24; 3001 x 150: ragged last gene and sample tile.
+_NO_NARROW = {"NMFC_NARROW": "0"}
+EUCLID_BATCHES = [(97, 33, (5,), 2, {}), (130, 17, (2, 3), 2, {}),
+                  (200, 60, (4,), 2, dict(_NO_NARROW, NMFC_AHTW_TILE="64")),
+                  (200, 60, (4,), 2, dict(_NO_NARROW, NMFC_AHTW_TILE="128")),
+                  (1100, 72, (2, 7, 10, 16), 3, {}), (1100, 72, (2, 7, 10, 16), 3, _NO_NARROW),
+                  (1100, 72, (2, 7, 10, 16), 3, {"NMFC_AHTW_TILE": "128"}), (3001, 150, (16, 9, 2), 2, {})]
+# the A h^T form each batch is there for, by position (the GPU test asserts that the run took it, from last_run_info)
+EUCLID_FORMS = ["narrow", "narrow", "64", "128", "64-kskip", "64-kskip", "128-kskip", "64-kskip"]
+EUCLID_ALL_FORMS = {"narrow", "64", "64-kskip", "128", "128-kskip"}
+assert len(EUCLID_FORMS) == len(EUCLID_BATCHES) and set(EUCLID_FORMS) == EUCLID_ALL_FORMS
+# runs that must give the same bits, by position: the two tiles of 200 x 60; 1100 x 72 under its three environments
+EUCLID_SAME_BITS = [(2, 3), (4, 5), (4, 6)]
+
+
+def euclid_kskip(n):
+    """Whether the A h^T kernels skip the padding half of the last K stage at this n (engine.hip plan_chunk)."""
+    return (n + 31) // 32 * 32 - n >= 8
+
+
+assert all(("kskip" in f) == euclid_kskip(c[1]) for f, c in zip(EUCLID_FORMS, EUCLID_BATCHES) if f != "narrow")
+
+
+def euclid_shapes():
+    return sorted({(m, n, k) for m, n, ks, _, _ in EUCLID_BATCHES for k in ks})
+
+
 def case_seed(kind, m, n, k):
     """The init seed of job 0 of a case: SEED, moved on for the cases of RESEED (where the luck of which large s_i
     meets which large r_i left one side's denominators all above or all below 1e-9)."""
@@ -278,7 +368,7 @@ def case_seed(kind, m, n, k):
 
 RESEED = {("mu", 37, 5, 5): 1, ("mu", 200, 16, 6): 1, ("mu", 200, 40, 5): 1, ("mu", 200, 64, 5): 1, ("mu", 300, 40, 5): 1,
           ("mu", 300, 64, 2): 1, ("mu", 300, 70, 3): 1, ("mu", 1000, 16, 8): 2, ("mu", 1000, 40, 3): 1,
-          ("mu", 3001, 150, 2): 5}
+          ("mu", 3001, 150, 2): 5, ("euclid", 3001, 150, 2): 2}
 
 
 # ---- the KL kernels at the corners of the domain they admit (test_gpu_widerange.py::test_kl_corners) -----------------
@@ -356,7 +446,7 @@ def reference(kind, m, n, k, job=0):
     A, W, H = case(kind, m, n, k, job)
     out = {}
     for T in (1, 2):
-        W, H = (ref_mu if kind == "mu" else ref_kl)(A, W, H, 1)
+        W, H = REF.get(kind, ref_kl)(A, W, H, 1)
         W.setflags(write=False)
         H.setflags(write=False)
         out[T] = (W, H)
@@ -370,12 +460,38 @@ def prefetch(kind, m, n, k, jobs):
         list(ex.map(lambda j: reference(kind, m, n, k, j), jobs))
 
 
+def measure_euclid(A, W0, H0):
+    """The Euclidean case from its reference alone, over T = 1 and 2: the smallest denominator of each side (den_min:
+    the rule divides without a guard); the smallest non-zero and the largest magnitude of any intermediate (numerator,
+    Gram entry, denominator, quotient, product); and, of the first update, the shares of all elements of H and of W
+    whose product old * q, the value eps is added to, is non-zero and below eps / 8 (lo) or above 8 eps (hi)."""
+    trace = []
+    ref_euclid(A, W0, H0, 2, trace=trace)
+    out = {"Hden_min": np.inf, "Wden_min": np.inf, "min": np.inf, "max": 0.0}
+    for it in trace:
+        for side in "HW":
+            out[f"{side}den_min"] = min(out[f"{side}den_min"], float(it[f"{side}den"].min()))
+        for X in it.values():
+            assert np.all(np.isfinite(X)) and np.all(X >= 0)
+            out["max"] = max(out["max"], float(X.max()))
+            if (X > 0).any():
+                out["min"] = min(out["min"], float(X[X > 0].min()))
+    e = LD(EUCLID_EPS)
+    for side, p in (("H", trace[0]["Hprod"]), ("W", trace[0]["Wquot"])):
+        out[f"{side}lo"] = float(np.mean((p > 0) & (p < e / 8)))
+        out[f"{side}hi"] = float(np.mean(p > 8 * e))
+    return out
+
+
 def measure(kind, m, n, k, seed=None):
     """What test_widerange_reference.py asserts about a case, from the reference alone: the smallest fraction over
     T = 1, 2 of rows of W / columns of H below 1e-9 of the norm; for MU the fractions of the non-zero denominators of the
-    first update below 1e-9 and above 1e-3 on each side; the smallest and largest positive value."""
+    first update below 1e-9 and above 1e-3 on each side; the smallest and largest positive value.  Euclid: what
+    measure_euclid returns."""
     A = wide_A(m, n, SEED, kind)
     W0, H0 = wide_init(m, n, k, case_seed(kind, m, n, k) if seed is None else seed, kind, 0)
+    if kind == "euclid":
+        return measure_euclid(A, W0, H0)
     out = {"belowW": 1.0, "belowH": 1.0, "min": np.inf, "max": 0.0}
     for T in (1, 2):
         if kind == "mu":
