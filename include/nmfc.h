@@ -266,7 +266,8 @@ int nmfc_calculate_norm_dev(const double* a, const double* w, const double* h, d
 int nmfc_calculate_maxchange_dev(const double* mat, double* mat0, int m, int n, double sqrteps, double* out,
                                  double* ms_out, void* stream);
 
-/* Frees the engine that nmf_mu (libnmf_compat.h) keeps across calls with the same A (its HBM and host copy). */
+/* Frees what nmf_mu (libnmf_compat.h) keeps across calls with the same A on each of its paths: the engine, the solo
+ * and the generic path's device copy of A, work buffers and stream, and the host copies of A. */
 void nmfc_nmf_mu_release(void);
 
 /* Diagnostics. */

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libnmf.so")
 SOURCES = ["engine.hip", "compat.hip", "brunet.hip", "generic.hip", "solo.hip", "hclust.cpp"]
-HEADERS = ["nmfc_kernels.hpp", "nmfc_tuning.hpp", "nmfc_internal.hpp", "lane_pool.hpp", "rmt.hpp", "../../include/nmfc.h", "../../include/libnmf_compat.h"]
+HEADERS = ["nmfc_kernels.hpp", "nmfc_tuning.hpp", "nmfc_internal.hpp", "nmfc_host.hpp", "lane_pool.hpp", "rmt.hpp", "../../include/nmfc.h", "../../include/libnmf_compat.h"]
 ARCH = os.environ.get("NMFC_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 

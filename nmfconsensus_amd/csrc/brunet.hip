@@ -24,7 +24,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,96 +31,22 @@
 #include <vector>
 
 #include "lane_pool.hpp"
+#include "nmfc_host.hpp"
 #include "nmfc_tuning.hpp"
 #include "rmt.hpp"
 #include "../../include/nmfc.h"
 #include "nmfc_internal.hpp"
+
+using nmfc_host::DevBuf;
+using nmfc_host::errorf;
+using nmfc_host::PinBuf;
+using nmfc_host::round_up;
 
 namespace {
 
 constexpr int BT = 256;
 constexpr int BR_KMAX = 16;
 constexpr double EPS = 2.220446049250313e-16;   // .Machine$double.eps
-
-void br_err(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-void br_err(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  nmfc_set_error(buf);
-}
-
-#define BCHECK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      br_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return -1;                                                                           \
-    }                                                                                      \
-  } while (0)
-
-long rup(long v, long a) { return (v + a - 1) / a * a; }
-
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int ensure(size_t need) {
-    if (need <= bytes) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    if (need == 0) return 0;
-    hipError_t e = hipMalloc(&p, need);
-    if (e != hipSuccess) {
-      br_err("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-      p = nullptr;
-      return -1;
-    }
-    bytes = need;
-    return 0;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-// Pinned host staging of one lane (the per-check stop-iteration read-back, the live-restart list, the seeds): the
-// small per-iteration copies of four lanes never go through HIP's shared pageable staging path.
-struct PinBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int ensure(size_t need) {
-    if (need <= bytes) return 0;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-    hipError_t e = hipHostMalloc(&p, need, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      br_err("hipHostMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-      p = nullptr;
-      return -1;
-    }
-    bytes = need;
-    return 0;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
 
 // q = a / p from a refined reciprocal r of p: q = a r and one residual correction (Markstein's final step), i.e. the
 // compiler's IEEE sequence without its operand-scaling steps (div_scale / div_fmas / div_fixup), which only matter
@@ -806,72 +731,29 @@ enum { BK_HNUM = 0, BK_HUPD = 1, BK_WUPD = 2, BK_DIV = 3, BK_N = 4 };
 
 struct BrLane {
   hipStream_t st = nullptr;
-  Buf W, H, Gp, RS, memb, nochange, stop_iter, act, seeds, labels;
-  Buf part, div;                 // divergence pass: per (restart, tile) partials, per restart D (only when enabled)
-  PinBuf h_si, h_act, h_seeds;   // pinned host mirrors of stop_iter, act, seeds
+  DevBuf W, H, Gp, RS, memb, nochange, stop_iter, act, seeds, labels;
+  DevBuf part, div;                 // divergence pass: per (restart, tile) partials, per restart D (only when enabled)
+  // pinned host mirrors of stop_iter, act, seeds: the small per-iteration copies of four lanes never go through HIP's
+  // shared pageable staging path
+  PinBuf h_si, h_act, h_seeds;
   PinBuf h_div;                  // ... and of div
   bool timing = false;
-  struct Pending {
-    int kid;
-    hipEvent_t a, b;
-  };
-  std::vector<Pending> pending;
-  std::vector<hipEvent_t> pool;
+  nmfc_host::LaunchTimer timer;
   double kms[BK_N] = {0, 0, 0, 0};
   long long kcount[BK_N] = {0, 0, 0, 0};
   double kfl_sum[BK_N] = {0, 0, 0, 0};
-  void release() {
-    Buf* bufs[] = {&W, &H, &Gp, &RS, &memb, &nochange, &stop_iter, &act, &seeds, &labels, &part, &div};
-    for (Buf* b : bufs) b->release();
-    h_si.release();
-    h_act.release();
-    h_seeds.release();
-    h_div.release();
-    for (auto v : pool) (void)hipEventDestroy(v);
-    pool.clear();
-    if (st) (void)hipStreamDestroy(st);
-    st = nullptr;
-  }
 };
 
-hipEvent_t br_event(BrLane* L) {
-  if (!L->pool.empty()) {
-    hipEvent_t v = L->pool.back();
-    L->pool.pop_back();
-    return v;
-  }
-  hipEvent_t v = nullptr;
-  if (hipEventCreate(&v) != hipSuccess) return nullptr;
-  return v;
-}
-
 void br_drain(BrLane* L) {
-  for (auto& p : L->pending) {
-    float ms = 0.f;
-    if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) L->kms[p.kid] += ms;
-    L->pool.push_back(p.a);
-    L->pool.push_back(p.b);
-  }
-  L->pending.clear();
+  L->timer.drain([L](int kid, float ms) { L->kms[kid] += ms; });
 }
 
+// counts the launch and its flops; HIP events on the lane's stream around it only when timing is enabled
 struct BTimed {
-  BrLane* L;
-  int kid;
-  hipEvent_t a = nullptr;
-  BTimed(BrLane* L_, int kid_, double flops) : L(L_), kid(kid_) {
+  nmfc_host::TimedScope scope;
+  BTimed(BrLane* L, int kid, double flops) : scope(L->timer, L->st, kid, L->timing) {
     L->kcount[kid] += 1;
     L->kfl_sum[kid] += flops;
-    if (L->timing && (a = br_event(L))) (void)hipEventRecord(a, L->st);
-  }
-  ~BTimed() {
-    if (L->timing && a) {
-      hipEvent_t b = br_event(L);
-      if (b) {
-        (void)hipEventRecord(b, L->st);
-        L->pending.push_back({kid, a, b});
-      }
-    }
   }
 };
 
@@ -884,7 +766,7 @@ struct nmfc_brunet {
   long m_pad = 0, n_pad = 0;
   int gc = 0, nchunks = 0;
   int nlanes = BR_LANES;
-  Buf Acm, Arm, counts_tmp, cons_tmp;
+  DevBuf Acm, Arm, counts_tmp, cons_tmp;
   BrLane lanes[BR_LANES];
   bool timing = false;
   double kms[BK_N] = {0, 0, 0, 0};
@@ -896,7 +778,7 @@ struct nmfc_brunet {
   int div_B = 0, div_rb = 0;
   std::vector<int> div_ks, best_slot;
   std::vector<double> div_vals;
-  std::vector<Buf> bestW, bestH;
+  std::vector<DevBuf> bestW, bestH;
 };
 
 namespace {
@@ -914,10 +796,10 @@ int br_iterate(const nmfc_brunet* e, BrLane* L, int B, const nmfc_brunet_opts& o
   int* si = L->h_si.as<int>();     // pinned read-back of stop_iter
   for (int b = 0; b < B; ++b) act[b] = b, si[b] = 0;
   int nact = B;
-  BCHECK(hipMemcpyAsync(L->act.p, act, sizeof(int) * B, hipMemcpyHostToDevice, st));
-  BCHECK(hipMemsetAsync(L->memb.p, 0, sizeof(int) * (size_t)B * n, st));   // old.membership starts at 0
-  BCHECK(hipMemsetAsync(L->nochange.p, 0, sizeof(int) * B, st));
-  BCHECK(hipMemsetAsync(L->stop_iter.p, 0, sizeof(int) * B, st));
+  HIPCHK(hipMemcpyAsync(L->act.p, act, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(L->memb.p, 0, sizeof(int) * (size_t)B * n, st));   // old.membership starts at 0
+  HIPCHK(hipMemsetAsync(L->nochange.p, 0, sizeof(int) * B, st));
+  HIPCHK(hipMemsetAsync(L->stop_iter.p, 0, sizeof(int) * B, st));
   const double fl = 4.0 * m * n * K;   // algorithmic flop per restart and kernel: VP (2mnk) + product (2mnk)
   for (int t = 1; t <= o.maxiter && nact > 0; ++t) {
     const int check = (t % o.stopfreq) == 0;
@@ -942,25 +824,25 @@ int br_iterate(const nmfc_brunet* e, BrLane* L, int B, const nmfc_brunet_opts& o
                          e->m_pad, m, n, L->act.as<int>(), nact, L->W.as<double>(), wstride, L->H.as<double>(), hstride,
                          L->RS.as<double>());
     }
-    BCHECK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     if (check) {
       // stops happen only on check iterations, after that iteration's W update (NMF.div breaks at the
       // end of the iteration): drop stopped restarts from the launch list
-      BCHECK(hipMemcpyAsync(si, L->stop_iter.p, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-      BCHECK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpyAsync(si, L->stop_iter.p, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
       if (L->timing) br_drain(L);
       int q = 0;
       for (int x = 0; x < nact; ++x)
         if (si[act[x]] == 0) act[q++] = act[x];
       if (q != nact) {
         nact = q;
-        if (nact > 0) BCHECK(hipMemcpyAsync(L->act.p, act, sizeof(int) * nact, hipMemcpyHostToDevice, st));
-        BCHECK(hipStreamSynchronize(st));
+        if (nact > 0) HIPCHK(hipMemcpyAsync(L->act.p, act, sizeof(int) * nact, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
       }
     }
   }
-  BCHECK(hipMemcpyAsync(si, L->stop_iter.p, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-  BCHECK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(si, L->stop_iter.p, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   if (L->timing) br_drain(L);
   iters.resize(B);
   stopped.resize(B);
@@ -982,7 +864,7 @@ int br_dispatch(const nmfc_brunet* e, BrLane* L, int K, int B, const nmfc_brunet
     BR_CASE(12) BR_CASE(13) BR_CASE(14) BR_CASE(15) BR_CASE(16)
 #undef BR_CASE
     default:
-      br_err("nmfc_brunet_run: k=%d unsupported", K);
+      errorf("nmfc_brunet_run: k=%d unsupported", K);
       return -1;
   }
 }
@@ -1019,16 +901,16 @@ int br_divergence(nmfc_brunet* e, BrLane* L, const KJob& kj, int B) {
       BR_DIV_CASE(16)
 #undef BR_DIV_CASE
       default:
-        br_err("nmfc_brunet_run: k=%d unsupported", K);
+        errorf("nmfc_brunet_run: k=%d unsupported", K);
         return -1;
     }
     hipLaunchKernelGGL(k_br_div_sum, dim3(B), dim3(64), 0, st, L->part.as<double>(), ntiles, (double)m * n,
                        L->div.as<double>());
   }
-  BCHECK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   double* d = L->h_div.as<double>();
-  BCHECK(hipMemcpyAsync(d, L->div.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-  BCHECK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(d, L->div.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   if (L->timing) br_drain(L);
   int best = 0;
   for (int b = 0; b < B; ++b) {
@@ -1036,16 +918,16 @@ int br_divergence(nmfc_brunet* e, BrLane* L, const KJob& kj, int B) {
     if (d[b] < d[best]) best = b;   // the lowest restart on ties
   }
   e->best_slot[kj.ki] = best;
-  BCHECK(hipMemcpyAsync(e->bestW[kj.ki].p, L->W.as<double>() + (size_t)best * m * K, wbytes, hipMemcpyDeviceToDevice, st));
-  BCHECK(hipMemcpyAsync(e->bestH[kj.ki].p, L->H.as<double>() + (size_t)best * n * K, hbytes, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->bestW[kj.ki].p, L->W.as<double>() + (size_t)best * m * K, wbytes, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->bestH[kj.ki].p, L->H.as<double>() + (size_t)best * n * K, hbytes, hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
 int br_run_k(nmfc_brunet* e, BrLane* L, const KJob& kj, int B, int R, const nmfc_brunet_opts& o, const double* W_init,
              const double* H_init, int32_t* dcounts, nmfc_result* out, long long* tot_iters, int* max_it) {
   const int m = e->m, n = e->n, K = kj.K, ki = kj.ki;
-  BCHECK(hipSetDevice(e->dev));
-  if (!L->st) BCHECK(hipStreamCreateWithFlags(&L->st, hipStreamNonBlocking));
+  HIPCHK(hipSetDevice(e->dev));
+  if (!L->st) HIPCHK(hipStreamCreateWithFlags(&L->st, hipStreamNonBlocking));
   hipStream_t st = L->st;
   if (L->W.ensure(sizeof(double) * (size_t)B * m * K) || L->H.ensure(sizeof(double) * (size_t)B * n * K) ||
       L->Gp.ensure(sizeof(double) * (size_t)e->nchunks * B * K * e->n_pad) ||
@@ -1059,7 +941,7 @@ int br_run_k(nmfc_brunet* e, BrLane* L, const KJob& kj, int B, int R, const nmfc
   uint32_t* seeds = L->h_seeds.as<uint32_t>();
   const int rb = std::max(0, o.restart_begin);
   for (int b = 0; b < B; ++b) seeds[b] = o.seed + (uint32_t)(rb + b + 1);   // set.seed(rseed + i), i 1-based
-  BCHECK(hipMemcpyAsync(L->seeds.p, seeds, sizeof(uint32_t) * B, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(L->seeds.p, seeds, sizeof(uint32_t) * B, hipMemcpyHostToDevice, st));
   if (W_init && H_init) {
     // caller factors for this k's B jobs: W_b m x K column-major, H_b K x n column-major; positive and within
     // [2^-60, 2^60] (the batched reciprocals' domain, recip_batch)
@@ -1067,7 +949,7 @@ int br_run_k(nmfc_brunet* e, BrLane* L, const KJob& kj, int B, int R, const nmfc
     for (size_t x = 0; x < nwk + nhk; ++x) {
       const double v = x < nwk ? W_init[kj.woff + x] : H_init[kj.hoff + (x - nwk)];
       if (!(v >= 0x1p-60 && v <= 0x1p60)) {
-        br_err("nmfc_brunet_run: caller factors must lie in [2^-60, 2^60] (k=%d: %g)", K, v);
+        errorf("nmfc_brunet_run: caller factors must lie in [2^-60, 2^60] (k=%d: %g)", K, v);
         return -1;
       }
     }
@@ -1076,34 +958,34 @@ int br_run_k(nmfc_brunet* e, BrLane* L, const KJob& kj, int B, int R, const nmfc
       for (int c = 0; c < K; ++c)
         for (int i = 0; i < m; ++i)
           hw[(size_t)b * wstride + (size_t)i * K + c] = W_init[kj.woff + (long)b * wstride + (long)c * m + i];
-    BCHECK(hipMemcpyAsync(L->W.p, hw.data(), sizeof(double) * hw.size(), hipMemcpyHostToDevice, st));
-    BCHECK(hipMemcpyAsync(L->H.p, H_init + kj.hoff, sizeof(double) * (size_t)B * hstride, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(L->W.p, hw.data(), sizeof(double) * hw.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(L->H.p, H_init + kj.hoff, sizeof(double) * (size_t)B * hstride, hipMemcpyHostToDevice, st));
   } else {
     hipLaunchKernelGGL(k_br_init, dim3(B), dim3(BT), 0, st, L->seeds.as<uint32_t>(), m, n, K, L->W.as<double>(), wstride,
                        L->H.as<double>(), hstride);
-    BCHECK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  BCHECK(hipStreamSynchronize(st));   // seeds / hw host buffers
+  HIPCHK(hipStreamSynchronize(st));   // seeds / hw host buffers
   std::vector<int> iters, stopped;
   if (br_dispatch(e, L, K, B, o, iters, stopped)) return -1;
   if (e->divergence && br_divergence(e, L, kj, B)) return -1;
   hipLaunchKernelGGL(k_br_labels, dim3((n + BT - 1) / BT, B), dim3(BT), 0, st, L->H.as<double>(), hstride, K, n,
                      L->labels.as<int32_t>());
-  BCHECK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (dcounts) {
     hipLaunchKernelGGL(k_br_counts, dim3((n + 15) / 16, (n + 15) / 16), dim3(BT), 0, st, L->labels.as<int32_t>(), B, n,
                        dcounts + (size_t)n * n * ki);
-    BCHECK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   if (out && out->labels)
-    BCHECK(hipMemcpyAsync(out->labels + (size_t)ki * B * n, L->labels.p, sizeof(int32_t) * (size_t)B * n,
+    HIPCHK(hipMemcpyAsync(out->labels + (size_t)ki * B * n, L->labels.p, sizeof(int32_t) * (size_t)B * n,
                           hipMemcpyDeviceToHost, st));
   if (out && (out->W || out->H)) {
     hw.resize((size_t)B * wstride);
     hh.resize((size_t)B * hstride);
-    BCHECK(hipMemcpyAsync(hw.data(), L->W.p, sizeof(double) * hw.size(), hipMemcpyDeviceToHost, st));
-    BCHECK(hipMemcpyAsync(hh.data(), L->H.p, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, st));
-    BCHECK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(hw.data(), L->W.p, sizeof(double) * hw.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hh.data(), L->H.p, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     if (out->W)
       for (int b = 0; b < B; ++b)
         for (int c = 0; c < K; ++c)
@@ -1111,7 +993,7 @@ int br_run_k(nmfc_brunet* e, BrLane* L, const KJob& kj, int B, int R, const nmfc
             out->W[kj.woff + (long)b * wstride + (long)c * m + i] = hw[(size_t)b * wstride + (size_t)i * K + c];
     if (out->H) memcpy(out->H + kj.hoff, hh.data(), sizeof(double) * hh.size());
   }
-  BCHECK(hipStreamSynchronize(st));
+  HIPCHK(hipStreamSynchronize(st));
   for (int b = 0; b < B; ++b) {
     *tot_iters += iters[b];
     *max_it = std::max(*max_it, iters[b]);
@@ -1140,12 +1022,12 @@ void nmfc_brunet_default_opts(nmfc_brunet_opts* o) {
 
 nmfc_brunet* nmfc_brunet_create(int device, const double* A, int m, int n, int a_on_device) {
   if (!A || m <= 0 || n <= 0) {
-    br_err("nmfc_brunet_create: bad arguments (A=%p m=%d n=%d)", (const void*)A, m, n);
+    errorf("nmfc_brunet_create: bad arguments (A=%p m=%d n=%d)", (const void*)A, m, n);
     return nullptr;
   }
   nmfc_brunet* e = new nmfc_brunet();
   auto fail = [&](const char* what, hipError_t err) -> nmfc_brunet* {
-    br_err("nmfc_brunet_create: %s: %s", what, hipGetErrorString(err));
+    nmfc_host::hip_fail("nmfc_brunet_create", what, err);
     nmfc_brunet_destroy(e);
     return nullptr;
   };
@@ -1156,10 +1038,10 @@ nmfc_brunet* nmfc_brunet_create(int device, const double* A, int m, int n, int a
   if (const char* s = getenv("NMFC_BRUNET_LANES")) e->nlanes = std::max(1, std::min(BR_LANES, atoi(s)));
   e->m = m;
   e->n = n;
-  e->m_pad = rup(m, BT);
-  e->n_pad = rup(n, BT);
+  e->m_pad = round_up(m, BT);
+  e->n_pad = round_up(n, BT);
   // fixed gene chunks (a function of m only): about 16 chunks of whole LDS tiles, at most 2048 genes
-  e->gc = (int)std::min<long>(2048, std::max<long>(TL, rup((m + 15) / 16, TL)));
+  e->gc = (int)std::min<long>(2048, std::max<long>(TL, round_up((m + 15) / 16, TL)));
   e->nchunks = (m + e->gc - 1) / e->gc;
   if (e->Acm.ensure(sizeof(double) * e->m_pad * n) || e->Arm.ensure(sizeof(double) * (size_t)m * e->n_pad)) {
     nmfc_brunet_destroy(e);
@@ -1168,7 +1050,7 @@ nmfc_brunet* nmfc_brunet_create(int device, const double* A, int m, int n, int a
   if ((err = hipMemsetAsync(e->Acm.p, 0, e->Acm.bytes, e->st)) != hipSuccess) return fail("memset", err);
   if ((err = hipMemsetAsync(e->Arm.p, 0, e->Arm.bytes, e->st)) != hipSuccess) return fail("memset", err);
   const double* dA = A;
-  Buf tmp;
+  DevBuf tmp;
   if (!a_on_device) {
     if (tmp.ensure(sizeof(double) * (size_t)m * n)) {
       nmfc_brunet_destroy(e);
@@ -1178,7 +1060,7 @@ nmfc_brunet* nmfc_brunet_create(int device, const double* A, int m, int n, int a
       return fail("upload A", err);
     dA = tmp.as<double>();
   }
-  Buf dbad;
+  DevBuf dbad;
   if (dbad.ensure(sizeof(int))) {
     nmfc_brunet_destroy(e);
     return nullptr;
@@ -1191,11 +1073,9 @@ nmfc_brunet* nmfc_brunet_create(int device, const double* A, int m, int n, int a
   if ((err = hipMemcpyAsync(&bad, dbad.p, sizeof(int), hipMemcpyDeviceToHost, e->st)) != hipSuccess)
     return fail("read-back", err);
   if ((err = hipStreamSynchronize(e->st)) != hipSuccess) return fail("sync", err);
-  tmp.release();
-  dbad.release();
   if (bad) {
     // the KL updates need A >= 0; the bound keeps the batched reciprocals' products normal (recip_batch)
-    br_err("nmfc_brunet_create: A must hold finite, non-negative entries of at most 2^64");
+    errorf("nmfc_brunet_create: A must hold finite, non-negative entries of at most 2^64");
     nmfc_brunet_destroy(e);
     return nullptr;
   }
@@ -1206,18 +1086,18 @@ int nmfc_brunet_device(const nmfc_brunet* e) { return e ? e->dev : -1; }
 
 void nmfc_brunet_destroy(nmfc_brunet* e) {
   if (!e) return;
-  if (e->st) (void)hipStreamSynchronize(e->st);
+  // every stream is synchronised before anything is freed and destroyed after everything is
+  hipStream_t sts[BR_LANES + 1] = {e->st};
+  for (int l = 0; l < BR_LANES; ++l) sts[l + 1] = e->lanes[l].st;
+  for (hipStream_t st : sts)
+    if (st) (void)hipStreamSynchronize(st);
   for (BrLane& L : e->lanes) {
-    if (L.st) (void)hipStreamSynchronize(L.st);
     br_drain(&L);
-    L.release();
+    L.timer.destroy_events();
   }
-  Buf* bufs[] = {&e->Acm, &e->Arm, &e->counts_tmp, &e->cons_tmp};
-  for (Buf* b : bufs) b->release();
-  for (Buf& b : e->bestW) b.release();
-  for (Buf& b : e->bestH) b.release();
-  if (e->st) (void)hipStreamDestroy(e->st);
-  delete e;
+  delete e;   // every DevBuf / PinBuf member frees itself
+  for (hipStream_t st : sts)
+    if (st) (void)hipStreamDestroy(st);
 }
 
 void nmfc_brunet_set_timing(nmfc_brunet* e, int enable) {
@@ -1238,11 +1118,11 @@ void nmfc_brunet_set_divergence(nmfc_brunet* e, int enable) {
 namespace {
 int div_ready(const nmfc_brunet* e, const char* who) {
   if (!e) {
-    br_err("%s: NULL engine", who);
+    errorf("%s: NULL engine", who);
     return -1;
   }
   if (!e->div_valid) {
-    br_err("%s: the last run on this engine had the divergence disabled (nmfc_brunet_set_divergence) or failed", who);
+    errorf("%s: the last run on this engine had the divergence disabled (nmfc_brunet_set_divergence) or failed", who);
     return -1;
   }
   return 0;
@@ -1252,7 +1132,7 @@ int div_ready(const nmfc_brunet* e, const char* who) {
 int nmfc_brunet_divergence(nmfc_brunet* e, double* div_out) {
   if (div_ready(e, "nmfc_brunet_divergence")) return -1;
   if (!div_out) {
-    br_err("nmfc_brunet_divergence: NULL output");
+    errorf("nmfc_brunet_divergence: NULL output");
     return -1;
   }
   memcpy(div_out, e->div_vals.data(), sizeof(double) * e->div_vals.size());
@@ -1261,15 +1141,12 @@ int nmfc_brunet_divergence(nmfc_brunet* e, double* div_out) {
 
 int nmfc_brunet_log_probe(nmfc_brunet* e, const double* x, int count, double* y) {
   if (!e || !x || !y || count <= 0) {
-    br_err("nmfc_brunet_log_probe: bad arguments");
+    errorf("nmfc_brunet_log_probe: bad arguments");
     return -1;
   }
-  BCHECK(hipSetDevice(e->dev));
-  Buf dx, dy;
-  if (dx.ensure(sizeof(double) * count) || dy.ensure(sizeof(double) * count)) {
-    dx.release();
-    return -1;
-  }
+  HIPCHK(hipSetDevice(e->dev));
+  DevBuf dx, dy;
+  if (dx.ensure(sizeof(double) * count) || dy.ensure(sizeof(double) * count)) return -1;
   hipError_t err = hipMemcpyAsync(dx.p, x, sizeof(double) * count, hipMemcpyHostToDevice, e->st);
   if (err == hipSuccess) {
     hipLaunchKernelGGL(k_br_log, dim3((count + BT - 1) / BT), dim3(BT), 0, e->st, dx.as<double>(), count, dy.as<double>());
@@ -1277,10 +1154,8 @@ int nmfc_brunet_log_probe(nmfc_brunet* e, const double* x, int count, double* y)
   }
   if (err == hipSuccess) err = hipMemcpyAsync(y, dy.p, sizeof(double) * count, hipMemcpyDeviceToHost, e->st);
   if (err == hipSuccess) err = hipStreamSynchronize(e->st);
-  dx.release();
-  dy.release();
   if (err != hipSuccess) {
-    br_err("nmfc_brunet_log_probe: %s", hipGetErrorString(err));
+    errorf("nmfc_brunet_log_probe: %s", hipGetErrorString(err));
     return -1;
   }
   return 0;
@@ -1289,44 +1164,36 @@ int nmfc_brunet_log_probe(nmfc_brunet* e, const double* x, int count, double* y)
 int nmfc_brunet_quot_probe(nmfc_brunet* e, const double* a, const double* p, int count, int batch, double* q_out,
                            double* r_out) {
   if (!e || !a || !p || !q_out || count <= 0 || batch < 1 || batch > BR_RCP_MAX || count % batch != 0) {
-    br_err("nmfc_brunet_quot_probe: bad arguments (count=%d must be a positive multiple of batch=%d in 1..%d)", count,
+    errorf("nmfc_brunet_quot_probe: bad arguments (count=%d must be a positive multiple of batch=%d in 1..%d)", count,
            batch, BR_RCP_MAX);
     return -1;
   }
-  BCHECK(hipSetDevice(e->dev));
+  HIPCHK(hipSetDevice(e->dev));
   const size_t bytes = sizeof(double) * (size_t)count;
   const int nb = count / batch;
-  Buf da, dp, dq, dr;
-  hipError_t err = hipSuccess;
-  const bool ok = !da.ensure(bytes) && !dp.ensure(bytes) && !dq.ensure(bytes) && !dr.ensure(bytes);
-  if (ok) {
-    err = hipMemcpyAsync(da.p, a, bytes, hipMemcpyHostToDevice, e->st);
-    if (err == hipSuccess) err = hipMemcpyAsync(dp.p, p, bytes, hipMemcpyHostToDevice, e->st);
-    if (err == hipSuccess) {
-      const dim3 grid((nb + BT - 1) / BT), block(BT);
-      const double *xa = da.as<double>(), *xp = dp.as<double>();
-      double *xq = dq.as<double>(), *xr = dr.as<double>();
-      static_assert(BR_RCP_MAX == 5, "nmfc_brunet_quot_probe: one case per batch size");
-      switch (batch) {
-        case 1: hipLaunchKernelGGL(k_br_quot<1>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
-        case 2: hipLaunchKernelGGL(k_br_quot<2>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
-        case 3: hipLaunchKernelGGL(k_br_quot<3>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
-        case 4: hipLaunchKernelGGL(k_br_quot<4>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
-        default: hipLaunchKernelGGL(k_br_quot<5>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
-      }
-      err = hipGetLastError();
+  DevBuf da, dp, dq, dr;
+  if (da.ensure(bytes) || dp.ensure(bytes) || dq.ensure(bytes) || dr.ensure(bytes)) return -1;
+  hipError_t err = hipMemcpyAsync(da.p, a, bytes, hipMemcpyHostToDevice, e->st);
+  if (err == hipSuccess) err = hipMemcpyAsync(dp.p, p, bytes, hipMemcpyHostToDevice, e->st);
+  if (err == hipSuccess) {
+    const dim3 grid((nb + BT - 1) / BT), block(BT);
+    const double *xa = da.as<double>(), *xp = dp.as<double>();
+    double *xq = dq.as<double>(), *xr = dr.as<double>();
+    static_assert(BR_RCP_MAX == 5, "nmfc_brunet_quot_probe: one case per batch size");
+    switch (batch) {
+      case 1: hipLaunchKernelGGL(k_br_quot<1>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+      case 2: hipLaunchKernelGGL(k_br_quot<2>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+      case 3: hipLaunchKernelGGL(k_br_quot<3>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+      case 4: hipLaunchKernelGGL(k_br_quot<4>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
+      default: hipLaunchKernelGGL(k_br_quot<5>, grid, block, 0, e->st, xa, xp, nb, xq, xr); break;
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(q_out, dq.p, bytes, hipMemcpyDeviceToHost, e->st);
-    if (err == hipSuccess && r_out) err = hipMemcpyAsync(r_out, dr.p, bytes, hipMemcpyDeviceToHost, e->st);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->st);
+    err = hipGetLastError();
   }
-  da.release();
-  dp.release();
-  dq.release();
-  dr.release();
-  if (!ok) return -1;
+  if (err == hipSuccess) err = hipMemcpyAsync(q_out, dq.p, bytes, hipMemcpyDeviceToHost, e->st);
+  if (err == hipSuccess && r_out) err = hipMemcpyAsync(r_out, dr.p, bytes, hipMemcpyDeviceToHost, e->st);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->st);
   if (err != hipSuccess) {
-    br_err("nmfc_brunet_quot_probe: %s", hipGetErrorString(err));
+    errorf("nmfc_brunet_quot_probe: %s", hipGetErrorString(err));
     return -1;
   }
   return 0;
@@ -1335,7 +1202,7 @@ int nmfc_brunet_quot_probe(nmfc_brunet* e, const double* a, const double* p, int
 int nmfc_brunet_best(nmfc_brunet* e, int32_t* best_restart_out, double* best_div_out, double* W_out, double* H_out) {
   if (div_ready(e, "nmfc_brunet_best")) return -1;
   const int m = e->m, n = e->n, nk = (int)e->div_ks.size();
-  BCHECK(hipSetDevice(e->dev));
+  HIPCHK(hipSetDevice(e->dev));
   std::vector<double> tmp;
   long woff = 0, hoff = 0;
   for (int ki = 0; ki < nk; ++ki) {
@@ -1344,14 +1211,14 @@ int nmfc_brunet_best(nmfc_brunet* e, int32_t* best_restart_out, double* best_div
     if (best_div_out) best_div_out[ki] = e->div_vals[(size_t)ki * e->div_B + b];
     if (W_out) {   // the lane layout [gene][K] to m x K column-major
       tmp.resize((size_t)m * K);
-      BCHECK(hipMemcpyAsync(tmp.data(), e->bestW[ki].p, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, e->st));
-      BCHECK(hipStreamSynchronize(e->st));
+      HIPCHK(hipMemcpyAsync(tmp.data(), e->bestW[ki].p, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, e->st));
+      HIPCHK(hipStreamSynchronize(e->st));
       for (int c = 0; c < K; ++c)
         for (int i = 0; i < m; ++i) W_out[woff + (long)c * m + i] = tmp[(size_t)i * K + c];
     }
     if (H_out) {
-      BCHECK(hipMemcpyAsync(H_out + hoff, e->bestH[ki].p, sizeof(double) * (size_t)n * K, hipMemcpyDeviceToHost, e->st));
-      BCHECK(hipStreamSynchronize(e->st));
+      HIPCHK(hipMemcpyAsync(H_out + hoff, e->bestH[ki].p, sizeof(double) * (size_t)n * K, hipMemcpyDeviceToHost, e->st));
+      HIPCHK(hipStreamSynchronize(e->st));
     }
     woff += (long)m * K;
     hoff += (long)n * K;
@@ -1363,7 +1230,7 @@ int nmfc_brunet_run(nmfc_brunet* e, const int* ks, int nk, int R, const nmfc_bru
                     const double* W_init, const double* H_init, nmfc_result* out) {
   if (e) e->div_valid = false;   // until this run has filled them
   if (!e || !ks || nk <= 0 || R <= 0) {
-    br_err("nmfc_brunet_run: bad arguments");
+    errorf("nmfc_brunet_run: bad arguments");
     return -1;
   }
   nmfc_brunet_opts o;
@@ -1373,23 +1240,23 @@ int nmfc_brunet_run(nmfc_brunet* e, const int* ks, int nk, int R, const nmfc_bru
     nmfc_brunet_default_opts(&o);
   const int m = e->m, n = e->n;
   if (o.maxiter < 1 || o.stopfreq < 1 || o.stopconv < 1) {
-    br_err("nmfc_brunet_run: maxiter, stopfreq and stopconv must be >= 1");
+    errorf("nmfc_brunet_run: maxiter, stopfreq and stopconv must be >= 1");
     return -1;
   }
   for (int q = 0; q < nk; ++q)
     if (ks[q] < 2 || ks[q] > BR_KMAX) {
-      br_err("nmfc_brunet_run: k=%d unsupported (need 2 <= k <= %d)", ks[q], BR_KMAX);
+      errorf("nmfc_brunet_run: k=%d unsupported (need 2 <= k <= %d)", ks[q], BR_KMAX);
       return -1;
     }
   const int rb = std::max(0, o.restart_begin);
   const int re = o.restart_end < 0 ? R : std::min(o.restart_end, R);
   if (rb >= re) {
-    br_err("nmfc_brunet_run: empty restart range [%d, %d)", rb, re);
+    errorf("nmfc_brunet_run: empty restart range [%d, %d)", rb, re);
     return -1;
   }
   o.restart_begin = rb;
   const int B = re - rb;
-  BCHECK(hipSetDevice(e->dev));
+  HIPCHK(hipSetDevice(e->dev));
   auto t0 = std::chrono::steady_clock::now();
   int32_t* dcounts = nullptr;
   const size_t nn = (size_t)n * n;
@@ -1458,13 +1325,13 @@ int nmfc_brunet_run(nmfc_brunet* e, const int* ks, int nk, int R, const nmfc_bru
       if (e->cons_tmp.ensure(sizeof(double) * nn * nk)) return -1;
       hipLaunchKernelGGL(k_br_divide, dim3((unsigned)((nn * nk + BT - 1) / BT)), dim3(BT), 0, st, dcounts, (double)R,
                          (long)(nn * nk), e->cons_tmp.as<double>());
-      BCHECK(hipGetLastError());
-      BCHECK(hipMemcpyAsync(out->consensus, e->cons_tmp.p, sizeof(double) * nn * nk, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(out->consensus, e->cons_tmp.p, sizeof(double) * nn * nk, hipMemcpyDeviceToHost, st));
     }
     if (out->counts && !out->counts_on_device)
-      BCHECK(hipMemcpyAsync(out->counts, dcounts, sizeof(int32_t) * nn * nk, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(out->counts, dcounts, sizeof(int32_t) * nn * nk, hipMemcpyDeviceToHost, st));
   }
-  BCHECK(hipStreamSynchronize(st));
+  HIPCHK(hipStreamSynchronize(st));
   e->div_valid = e->divergence;
   auto t1 = std::chrono::steady_clock::now();
   if (out) {

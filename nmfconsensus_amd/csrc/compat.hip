@@ -16,6 +16,7 @@
 
 #include "../../include/libnmf_compat.h"
 #include "../../include/nmfc.h"
+#include "nmfc_host.hpp"
 #include "nmfc_internal.hpp"
 #include "nmfc_kernels.hpp"
 
@@ -118,35 +119,66 @@ void generateMatrix(const int* pm, const int* pn, const int* pk, init_t* pinit, 
   }
 }
 
-// The engine behind nmf_mu is kept across calls with the same A (nmf.r calls nmf_mu once per restart on
-// one data matrix, nmf.r:41-45; R passes a fresh copy each time, so A is matched by shape and content: a
-// host copy of the cached A is compared byte for byte, one pass over A like the hash it replaces, and no
-// collision can reuse a stale A).  Creating an engine uploads A and builds its two layouts, and its first run
-// allocates the work buffers: on the gct shape that is several times the whole MU loop.  A failed run drops
-// the cached engine.  NMFC_NMF_MU_CACHE=0 disables the cache; nmfc_nmf_mu_release() frees it (HBM + host copy).
+// The engine behind nmf_mu is kept across calls with the same A (matched as nmfc_host::MatrixKey does).  Creating an
+// engine uploads A and builds its two layouts, and its first run allocates the work buffers: on the gct shape that
+// is several times the whole MU loop.  A failed run drops the cached engine (it may be in a broken state).
+// NMFC_NMF_MU_CACHE=0 runs on an engine of the call's own, without the cache or its lock; nmfc_nmf_mu_release()
+// frees what all three arms keep: this engine and the solo and generic arms' buffers (HBM + host copies).
 namespace {
-std::mutex g_mu_lock;
-struct MuCache {
+struct MuCache : nmfc_host::MuCacheBase {
   nmfc_engine* e = nullptr;
-  int m = 0, n = 0;
-  std::vector<double>* a = nullptr;   // host copy of the cached A (no destructor: HIP may be torn down at exit)
-} g_mu;
+  void drop() {   // lock held
+    nmfc_engine_destroy(e);
+    e = nullptr;
+    drop_key();
+  }
+};
+MuCache& g_mu = *new MuCache;   // never destroyed (nmfc_host.hpp, process exit)
 
-void mu_cache_drop() {   // g_mu_lock held
-  nmfc_engine_destroy(g_mu.e);
-  g_mu.e = nullptr;
-  g_mu.m = g_mu.n = 0;
-  delete g_mu.a;
-  g_mu.a = nullptr;
+// one restart on engine e: the team launch where the shape allows it, else the batched engine with a batch of one
+int mu_engine_call(nmfc_engine* e, int m, int n, int k, int maxiter, double* w0, double* h0, int32_t* iters,
+                   int32_t* early) {
+  // small shapes (the bundled gct, expression sets up to 8192 genes x 64 samples): one team launch with a single
+  // upload / download (nmfc_engine_mu1); any other shape: the batched engine with a batch of one restart
+  const long m_pad = ((long)m + 127) / 128 * 128;
+  const char* team_env = getenv("NMFC_SMALL_KERNEL");
+  const char* small_env = getenv("NMFC_SMALL");
+  const bool team = m_pad <= 8192 && n <= 64 && !(team_env && strcmp(team_env, "single") == 0) &&
+                    !(small_env && atoi(small_env) == 0);
+  int rc = -1;
+  if (team) {
+    // w0/h0 are written only on success; a team that could not meet (its workgroups not all resident, e.g.
+    // many processes sharing the GPU, as BatchJobs njobs > 1 does) reports it instead of hanging, and the
+    // restart then runs on the batched engine, whose launches never wait for each other
+    // NMFC_TEAM_FAIL=1 (tests only) takes the fallback as if the team had failed
+    const char* tf = getenv("NMFC_TEAM_FAIL");
+    if (!(tf && atoi(tf) != 0)) rc = nmfc_engine_mu1(e, k, maxiter, NMFC_STOP_REF_COMPAT, w0, h0, w0, h0, iters, early);
+  }
+  if (rc != 0) {
+    nmfc_sweep_opts o;
+    nmfc_default_opts(&o);
+    o.maxiter = maxiter;
+    o.stop_rule = NMFC_STOP_REF_COMPAT;
+    o.check_every = 64;
+    nmfc_result r = {};
+    r.iters = iters;
+    r.stopped_early = early;
+    r.W = w0;
+    r.H = h0;
+    const int ks[1] = {k};
+    rc = nmfc_engine_run(e, ks, 1, 1, &o, w0, h0, &r);
+  }
+  return rc;
 }
 }  // namespace
 
 void nmfc_nmf_mu_release(void) {
   {
-    std::lock_guard<std::mutex> lock(g_mu_lock);
-    mu_cache_drop();
+    std::lock_guard<std::mutex> lock(g_mu.lock);
+    g_mu.drop();
   }
   nmfc_solo_release();
+  nmfc_generic_release();
 }
 
 // nmf_mu.c:84-315 on the GPU engine
@@ -195,68 +227,22 @@ double nmf_mu(double* a, double* w0, double* h0, int* pm, int* pn, int* pk, int*
     printf("Exiting nmf_mu after %i\n", printed);
     return 0;
   }
-  const char* cache_env = getenv("NMFC_NMF_MU_CACHE");
-  const bool cache = !(cache_env && atoi(cache_env) == 0);
-  std::unique_lock<std::mutex> lock(g_mu_lock, std::defer_lock);
-  nmfc_engine* e = nullptr;
-  if (cache) {
-    lock.lock();
-    const size_t len = (size_t)m * n;
-    if (g_mu.e && g_mu.m == m && g_mu.n == n && memcmp(g_mu.a->data(), a, len * sizeof(double)) == 0) {
-      e = g_mu.e;
-    } else {
-      mu_cache_drop();
-      e = nmfc_engine_create(-1, a, m, n, 0);
-      if (e) {
-        g_mu.e = e;
-        g_mu.m = m;
-        g_mu.n = n;
-        g_mu.a = new std::vector<double>(a, a + len);
-      }
-    }
-  } else {
-    e = nmfc_engine_create(-1, a, m, n, 0);
-  }
-  if (!e) {
-    fprintf(stderr, "Error in nmf_mu: %s\n", nmfc_last_error());
-    return -1;
-  }
   int32_t iters = 0, early = 0;
-  // small shapes (the bundled gct, expression sets up to 8192 genes x 64 samples): one team launch with a single
-  // upload / download (nmfc_engine_mu1); any other shape: the batched engine with a batch of one restart
-  const long m_pad = ((long)m + 127) / 128 * 128;
-  const char* team_env = getenv("NMFC_SMALL_KERNEL");
-  const char* small_env = getenv("NMFC_SMALL");
-  const bool team = m_pad <= 8192 && n <= 64 && !(team_env && strcmp(team_env, "single") == 0) &&
-                    !(small_env && atoi(small_env) == 0);
   int rc = -1;
-  if (team) {
-    // w0/h0 are written only on success; a team that could not meet (its workgroups not all resident, e.g.
-    // many processes sharing the GPU, as BatchJobs njobs > 1 does) reports it instead of hanging, and the
-    // restart then runs on the batched engine, whose launches never wait for each other
-    // NMFC_TEAM_FAIL=1 (tests only) takes the fallback as if the team had failed
-    const char* tf = getenv("NMFC_TEAM_FAIL");
-    if (!(tf && atoi(tf) != 0))
-      rc = nmfc_engine_mu1(e, k, *maxiter, NMFC_STOP_REF_COMPAT, w0, h0, w0, h0, &iters, &early);
-  }
-  if (rc != 0) {
-    nmfc_sweep_opts o;
-    nmfc_default_opts(&o);
-    o.maxiter = *maxiter;
-    o.stop_rule = NMFC_STOP_REF_COMPAT;
-    o.check_every = 64;
-    nmfc_result r = {};
-    r.iters = &iters;
-    r.stopped_early = &early;
-    r.W = w0;
-    r.H = h0;
-    const int ks[1] = {k};
-    rc = nmfc_engine_run(e, ks, 1, 1, &o, w0, h0, &r);
-  }
-  if (!cache)
+  if (!nmfc_host::mu_cache_enabled()) {
+    nmfc_engine* e = nmfc_engine_create(-1, a, m, n, 0);
+    if (e) rc = mu_engine_call(e, m, n, k, *maxiter, w0, h0, &iters, &early);
     nmfc_engine_destroy(e);
-  else if (rc != 0)
-    mu_cache_drop();   // the engine may be in a broken state: never reuse it
+  } else {
+    rc = nmfc_host::cached_call(g_mu, "nmf_mu", [&] {
+      if (!(g_mu.e && g_mu.key.same(a, m, n))) {
+        g_mu.drop();
+        if (!(g_mu.e = nmfc_engine_create(-1, a, m, n, 0))) return -1;
+        g_mu.key.set(a, m, n);
+      }
+      return mu_engine_call(g_mu.e, m, n, k, *maxiter, w0, h0, &iters, &early);
+    });
+  }
   if (rc != 0) {
     fprintf(stderr, "Error in nmf_mu: %s\n", nmfc_last_error());
     return -1;
@@ -375,40 +361,33 @@ done:
 // calculatenorm.c:44-78 -- host operands: upload, nmfc_calculate_norm_dev, download d.
 double calculateNorm(double* a, double* w, double* h, double* d, int m, int n, int k) {
   const size_t la = (size_t)m * n, lw = (size_t)m * k, lh = (size_t)k * n;
-  double *da = nullptr, *dw = nullptr, *dh = nullptr, *dd = nullptr;
-  double result = NAN, v = 0.0;
-  if (hipMalloc(&da, la * 8) || hipMalloc(&dw, lw * 8) || hipMalloc(&dh, lh * 8) || hipMalloc(&dd, la * 8)) goto done;
-  if (hipMemcpy(da, a, la * 8, hipMemcpyHostToDevice) || hipMemcpy(dw, w, lw * 8, hipMemcpyHostToDevice) ||
-      hipMemcpy(dh, h, lh * 8, hipMemcpyHostToDevice))
-    goto done;
-  if (nmfc_calculate_norm_dev(da, dw, dh, dd, m, n, k, &v, nullptr, nullptr) != 0) goto done;
-  if (hipMemcpy(d, dd, la * 8, hipMemcpyDeviceToHost)) goto done;
-  result = v;
-done:
-  if (std::isnan(result)) fprintf(stderr, "calculateNorm: device failure\n");
-  (void)hipFree(da);
-  (void)hipFree(dw);
-  (void)hipFree(dh);
-  (void)hipFree(dd);
-  return result;
+  nmfc_host::DevBuf da, dw, dh, dd;
+  double v = 0.0;
+  if (da.ensure(la * 8) || dw.ensure(lw * 8) || dh.ensure(lh * 8) || dd.ensure(la * 8) ||
+      hipMemcpy(da.p, a, la * 8, hipMemcpyHostToDevice) || hipMemcpy(dw.p, w, lw * 8, hipMemcpyHostToDevice) ||
+      hipMemcpy(dh.p, h, lh * 8, hipMemcpyHostToDevice) ||
+      nmfc_calculate_norm_dev(da.as<double>(), dw.as<double>(), dh.as<double>(), dd.as<double>(), m, n, k, &v, nullptr,
+                              nullptr) != 0 ||
+      hipMemcpy(d, dd.p, la * 8, hipMemcpyDeviceToHost)) {
+    fprintf(stderr, "calculateNorm: device failure\n");
+    return NAN;
+  }
+  return v;
 }
 
 // calculatemaxchange.c:42-71 -- host operands: upload, nmfc_calculate_maxchange_dev, download mat0.
 double calculateMaxchange(double* mat, double* mat0, int m, int n, const double sqrteps) {
   const size_t len = (size_t)m * n;
-  double *dm = nullptr, *dm0 = nullptr;
-  double result = NAN, v = 0.0;
-  if (hipMalloc(&dm, len * 8) || hipMalloc(&dm0, len * 8)) goto done;
-  if (hipMemcpy(dm, mat, len * 8, hipMemcpyHostToDevice) || hipMemcpy(dm0, mat0, len * 8, hipMemcpyHostToDevice))
-    goto done;
-  if (nmfc_calculate_maxchange_dev(dm, dm0, m, n, sqrteps, &v, nullptr, nullptr) != 0) goto done;
-  if (hipMemcpy(mat0, dm0, len * 8, hipMemcpyDeviceToHost)) goto done;
-  result = v;
-done:
-  if (std::isnan(result)) fprintf(stderr, "calculateMaxchange: device failure\n");
-  (void)hipFree(dm);
-  (void)hipFree(dm0);
-  return result;
+  nmfc_host::DevBuf dm, dm0;
+  double v = 0.0;
+  if (dm.ensure(len * 8) || dm0.ensure(len * 8) || hipMemcpy(dm.p, mat, len * 8, hipMemcpyHostToDevice) ||
+      hipMemcpy(dm0.p, mat0, len * 8, hipMemcpyHostToDevice) ||
+      nmfc_calculate_maxchange_dev(dm.as<double>(), dm0.as<double>(), m, n, sqrteps, &v, nullptr, nullptr) != 0 ||
+      hipMemcpy(mat0, dm0.p, len * 8, hipMemcpyDeviceToHost)) {
+    fprintf(stderr, "calculateMaxchange: device failure\n");
+    return NAN;
+  }
+  return v;
 }
 
 }  // extern "C"

@@ -15,7 +15,6 @@
 #include <chrono>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,68 +22,19 @@
 #include <vector>
 
 #include "../../include/nmfc.h"
+#include "nmfc_host.hpp"
 #include "nmfc_internal.hpp"
 #include "nmfc_kernels.hpp"
 
 using namespace nmfc;
+using nmfc_host::DevBuf;
+using nmfc_host::errorf;
+using nmfc_host::PinBuf;
+using nmfc_host::round_up;
 
 namespace {
 
 thread_local std::string g_err;
-
-void set_err(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-}
-
-#define HCHECK(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return -1;                                                                            \
-    }                                                                                       \
-  } while (0)
-
-long round_up(long v, long a) { return (v + a - 1) / a * a; }
-
-// Device buffer, released on destruction (every early return frees what it allocated).
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  int ensure(size_t need) {
-    if (need <= bytes) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    if (need == 0) return 0;
-    hipError_t e = hipMalloc(&p, need);
-    if (e != hipSuccess) {
-      set_err("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-      p = nullptr;
-      return -1;
-    }
-    bytes = need;
-    return 0;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
 
 // 31x31 jump matrices J[c] = M^(c * rchunk) mod 2^32 of the recurrence r[i] = r[i-31] + r[i-3]
 // acting on the ordered window (r[i-31], ..., r[i-1]).
@@ -314,21 +264,15 @@ struct nmfc_engine {
   // its own partial buffers and flags (zeroed when allocated; tags continue from mu1_base, the iterations of
   // earlier calls)
   DevBuf mu1_dev, mu1_G, mu1_SW, mu1_flag;
-  char* mu1_host = nullptr;
-  size_t mu1_host_bytes = 0;
+  PinBuf mu1_host;
   int mu1_base = -1;   // -1: the flags must be zeroed
   int mu1_kprev = 16;  // staging rows [k, mu1_kprev) may hold a previous call's factors
   int jump_chunks = 0, jump_rchunk = 0;   // the jump table on the device: chunks, draws per chunk
-  int* h_stopped = nullptr;   // pinned, 2 slots
+  PinBuf h_stopped;   // 2 ints
   // timing
   bool timing = false;
   int timing_stride = 1;            // time the launches of every timing_stride-th MU iteration
-  std::vector<hipEvent_t> ev_pool;
-  struct Pending {
-    int kid;
-    hipEvent_t a, b;
-  };
-  std::vector<Pending> pending;
+  nmfc_host::LaunchTimer timer;
   double kms[KID_N] = {0};
   long long kcount[KID_N] = {0};    // timed launches (event pairs drained)
   long long klaunch[KID_N] = {0};   // every launch
@@ -473,7 +417,7 @@ int launch_team(nmfc_engine* e, int nblocks, int maxiter, int stop_rule) {
   const int jb = (e->n + 15) / 16;
   const int P = (int)(e->m_pad / TEAM_ROWS);
   if (e->m_pad % TEAM_ROWS != 0 || P > TEAM_PMAX || jb < 1 || jb > 4) {
-    set_err("k_team_mu: m_pad %ld / n %d unsupported", e->m_pad, e->n);
+    errorf("k_team_mu: m_pad %ld / n %d unsupported", e->m_pad, e->n);
     return -1;
   }
   auto kern = jb == 1 ? k_team_mu<1> : jb == 2 ? k_team_mu<2> : jb == 3 ? k_team_mu<3> : k_team_mu<4>;
@@ -484,7 +428,7 @@ int launch_team(nmfc_engine* e, int nblocks, int maxiter, int stop_rule) {
       e->teamFlag.ensure(sizeof(unsigned) * (nteams * TEAM_PMAX + 16)))
     return -1;
   // flags zeroed per launch (tags start at 1); the error word sits behind them
-  HCHECK(hipMemsetAsync(e->teamFlag.p, 0, sizeof(unsigned) * (nteams * TEAM_PMAX + 16), e->st));
+  HIPCHK(hipMemsetAsync(e->teamFlag.p, 0, sizeof(unsigned) * (nteams * TEAM_PMAX + 16), e->st));
   hipLaunchKernelGGL(kern, dim3(nteams * P), dim3(256), 0, e->st, e->smallblk.as<SmallBlock>(), nblocks, P,
                      e->Acm.as<double>(), e->m_pad, e->n, e->n_pad, e->W[0].as<double>(), e->H[0].as<double>(), maxiter,
                      stop_rule, e->stop_iter.as<int>(), e->stop_reason.as<int>(), e->teamG.as<double>(),
@@ -492,7 +436,7 @@ int launch_team(nmfc_engine* e, int nblocks, int maxiter, int stop_rule) {
                      reinterpret_cast<int*>(e->teamFlag.as<unsigned>() + nteams * TEAM_PMAX), nullptr);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
-    set_err("k_team_mu launch: %s", hipGetErrorString(err));
+    errorf("k_team_mu launch: %s", hipGetErrorString(err));
     return -1;
   }
   return 0;
@@ -522,7 +466,7 @@ int launch_small(nmfc_engine* e, int nblocks, int maxiter, int stop_rule) {
   hipError_t err;
   const int jb = (e->n + 15) / 16;
   if (e->m_pad % 64 != 0 || e->n_pad != (jb <= 2 ? 32 : 64)) {   // k_small_mu's compile-time strides
-    set_err("k_small_mu: m_pad %ld / n_pad %ld unsupported for n = %d", e->m_pad, e->n_pad, e->n);
+    errorf("k_small_mu: m_pad %ld / n_pad %ld unsupported for n = %d", e->m_pad, e->n_pad, e->n);
     return -1;
   }
   // eight waves where the genes split into an even number of 16-gene blocks per wave (m_pad a multiple of 256),
@@ -533,7 +477,7 @@ int launch_small(nmfc_engine* e, int nblocks, int maxiter, int stop_rule) {
       case 4: err = launch_small_g<4, 8>(e, nblocks, maxiter, stop_rule); break;
       case 6: err = launch_small_g<6, 8>(e, nblocks, maxiter, stop_rule); break;
       case 8: err = launch_small_g<8, 8>(e, nblocks, maxiter, stop_rule); break;
-      default: set_err("k_small_mu: m_pad %ld unsupported", e->m_pad); return -1;
+      default: errorf("k_small_mu: m_pad %ld unsupported", e->m_pad); return -1;
     }
   } else {
     switch (e->m_pad / 64) {
@@ -545,69 +489,35 @@ int launch_small(nmfc_engine* e, int nblocks, int maxiter, int stop_rule) {
       case 12: err = launch_small_g<12, 4>(e, nblocks, maxiter, stop_rule); break;
       case 14: err = launch_small_g<14, 4>(e, nblocks, maxiter, stop_rule); break;
       case 16: err = launch_small_g<16, 4>(e, nblocks, maxiter, stop_rule); break;
-      default: set_err("k_small_mu: m_pad %ld unsupported", e->m_pad); return -1;
+      default: errorf("k_small_mu: m_pad %ld unsupported", e->m_pad); return -1;
     }
   }
   if (err != hipSuccess) {
-    set_err("k_small_mu launch: %s", hipGetErrorString(err));
+    errorf("k_small_mu launch: %s", hipGetErrorString(err));
     return -1;
   }
   return 0;
 }
 
-hipEvent_t take_event(nmfc_engine* e) {
-  if (!e->ev_pool.empty()) {
-    hipEvent_t ev = e->ev_pool.back();
-    e->ev_pool.pop_back();
-    return ev;
-  }
-  hipEvent_t ev;
-  if (hipEventCreate(&ev) != hipSuccess) return nullptr;
-  return ev;
-}
-
 void drain_timing(nmfc_engine* e) {
-  for (auto& pnd : e->pending) {
-    float ms = 0.f;
-    if (hipEventSynchronize(pnd.b) == hipSuccess && hipEventElapsedTime(&ms, pnd.a, pnd.b) == hipSuccess) {
-      e->kms[pnd.kid] += ms;
-      e->kcount[pnd.kid] += 1;
-    }
-    e->ev_pool.push_back(pnd.a);
-    e->ev_pool.push_back(pnd.b);
-  }
-  e->pending.clear();
+  e->timer.drain([e](int kid, float ms) {
+    e->kms[kid] += ms;
+    e->kcount[kid] += 1;
+  });
 }
 
 // HIP events on the engine's stream around one launch (only when timing is enabled)
 struct TimedLaunch {
-  nmfc_engine* e;
-  int kid;
-  hipEvent_t a = nullptr;
+  nmfc_host::TimedScope scope;
   // sample = false: counted, not timed (the MU loop times every timing_stride-th iteration)
-  TimedLaunch(nmfc_engine* e_, int kid_, bool sample = true) : e(e_), kid(kid_) {
+  TimedLaunch(nmfc_engine* e, int kid, bool sample = true) : scope(e->timer, e->st, kid, e->timing && sample) {
     e->klaunch[kid] += 1;
-    if (e->timing && sample) {
-      a = take_event(e);
-      if (a) (void)hipEventRecord(a, e->st);
-    }
-  }
-  ~TimedLaunch() {
-    if (a) {
-      hipEvent_t b = take_event(e);
-      if (b) {
-        (void)hipEventRecord(b, e->st);
-        e->pending.push_back({kid, a, b});
-      } else {
-        e->ev_pool.push_back(a);
-      }
-    }
   }
 };
 
 // ---- nmfc_engine_run: the state of one call and its phases, in the order they run (DESIGN.md "The sweep driver") ----
 
-struct PollEvents {   // destroyed on every exit path, including HCHECK returns
+struct PollEvents {   // destroyed on every exit path, including HIPCHK returns
   hipEvent_t ev[2] = {nullptr, nullptr};
   ~PollEvents() {
     for (hipEvent_t x : ev)
@@ -667,7 +577,7 @@ void transpose(const double* src, int rows, int cols, double* dst) {
 
 int check_args(Sweep& s, nmfc_engine* e, const int* ks, int nk, int R, const nmfc_sweep_opts* opts_in) {
   if (!e || !ks || nk <= 0 || R <= 0) {
-    set_err("nmfc_engine_run: bad arguments");
+    errorf("nmfc_engine_run: bad arguments");
     return -1;
   }
   s.e = e;
@@ -684,28 +594,28 @@ int check_args(Sweep& s, nmfc_engine* e, const int* ks, int nk, int R, const nmf
   for (int i = 0; i < nk; ++i) {
     // nmf.r:107-108 rejects k = 1; the per-restart LDS blocks hold k <= KMAX.
     if (ks[i] < 2 || ks[i] > KMAX || ks[i] > n || ks[i] > m) {
-      set_err("nmfc_engine_run: k=%d unsupported (need 2 <= k <= min(%d, m, n))", ks[i], KMAX);
+      errorf("nmfc_engine_run: k=%d unsupported (need 2 <= k <= min(%d, m, n))", ks[i], KMAX);
       return -1;
     }
     // k_init walks a restart's m k + k n draws with 32-bit draw indices (one chunk of up to 31 x 32 past the end)
     if ((long)m * ks[i] + (long)ks[i] * n + 31L * 32 >= (long)INT_MAX) {
-      set_err("nmfc_engine_run: m k + k n = %ld draws per restart exceeds the init kernel's 32-bit index range",
-              (long)m * ks[i] + (long)ks[i] * n);
+      errorf("nmfc_engine_run: m k + k n = %ld draws per restart exceeds the init kernel's 32-bit index range",
+             (long)m * ks[i] + (long)ks[i] * n);
       return -1;
     }
   }
   if (opts.maxiter < 0) {
-    set_err("nmfc_engine_run: maxiter must be >= 0");
+    errorf("nmfc_engine_run: maxiter must be >= 0");
     return -1;
   }
   if (opts.stop_rule < 0 || opts.stop_rule > 3 || opts.label_rule < 0 || opts.label_rule > 1 ||
       opts.init_stream < 0 || opts.init_stream > 1) {
-    set_err("nmfc_engine_run: bad stop rule, label rule or init stream");
+    errorf("nmfc_engine_run: bad stop rule, label rule or init stream");
     return -1;
   }
   // nmfc_engine_set_euclid: FIXED means fixed, every other value (the default included) the script's membership rule
   if (e->euclid) opts.stop_rule = opts.stop_rule == NMFC_STOP_FIXED ? STOP_FIXED : STOP_MEMBER;
-  HCHECK(hipSetDevice(e->dev));
+  HIPCHK(hipSetDevice(e->dev));
   return 0;
 }
 
@@ -725,7 +635,7 @@ int plan_jobs(Sweep& s) {
   const long jb = std::max(0, s.opts.job_begin);
   const long je = (s.opts.job_end < 0) ? njobs_all : std::min<long>(s.opts.job_end, njobs_all);
   if (jb >= je) {
-    set_err("nmfc_engine_run: empty job range [%ld, %ld)", jb, je);
+    errorf("nmfc_engine_run: empty job range [%ld, %ld)", jb, je);
     return -1;
   }
   s.jb = jb;
@@ -778,11 +688,11 @@ int plan_jobs(Sweep& s) {
 
 int upload_packing(nmfc_engine* e, const Packing& p) {
   hipStream_t st = e->st;
-  HCHECK(hipMemcpyAsync(e->rinfo.p, p.ri.data(), sizeof(RestartInfo) * std::max<size_t>(p.ri.size(), 1),
+  HIPCHK(hipMemcpyAsync(e->rinfo.p, p.ri.data(), sizeof(RestartInfo) * std::max<size_t>(p.ri.size(), 1),
                         hipMemcpyHostToDevice, st));
-  HCHECK(hipMemcpyAsync(e->prb.p, p.prb.data(), sizeof(int) * p.npanels, hipMemcpyHostToDevice, st));
-  HCHECK(hipMemcpyAsync(e->pre.p, p.pre.data(), sizeof(int) * p.npanels, hipMemcpyHostToDevice, st));
-  HCHECK(hipMemcpyAsync(e->colinfo.p, p.ci.data(), sizeof(ColInfo) * p.ci.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->prb.p, p.prb.data(), sizeof(int) * p.npanels, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->pre.p, p.pre.data(), sizeof(int) * p.npanels, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->colinfo.p, p.ci.data(), sizeof(ColInfo) * p.ci.size(), hipMemcpyHostToDevice, st));
   return 0;
 }
 
@@ -810,17 +720,17 @@ int ensure_buffers(Sweep& s) {
   if (s.tolx && e->Wsnap.ensure(sizeof(double) * cap_cols * e->m_pad)) return -1;
   hipStream_t st = e->st;
   if (upload_packing(e, pk)) return -1;
-  HCHECK(hipMemcpyAsync(e->slot.p, s.rslot.data(), sizeof(int) * nj, hipMemcpyHostToDevice, st));
-  HCHECK(hipMemsetAsync(e->stop_iter.p, 0, sizeof(int) * nj, st));
-  HCHECK(hipMemsetAsync(e->stop_reason.p, 0, sizeof(int) * nj, st));
-  HCHECK(hipMemsetAsync(e->unchanged.p, 0, sizeof(int) * nj, st));
-  HCHECK(hipMemsetAsync(e->classes.p, 0, sizeof(int) * nj * s.cls_ld, st));   // nmf_mu.c:132 zero start
-  HCHECK(hipMemsetAsync(e->n_stopped.p, 0, sizeof(int), st));
-  HCHECK(hipMemsetAsync(e->colact.p, 0, sizeof(int) * cap_cols, st));
-  HCHECK(hipMemsetAsync(e->W[0].p, 0, sizeof(double) * cap_cols * e->m_pad, st));
-  HCHECK(hipMemsetAsync(e->H[0].p, 0, sizeof(double) * cap_cols * e->n_pad, st));
-  HCHECK(hipMemsetAsync(e->W[1].p, 0, sizeof(double) * cap_cols * e->m_pad, st));
-  HCHECK(hipMemsetAsync(e->H[1].p, 0, sizeof(double) * cap_cols * e->n_pad, st));
+  HIPCHK(hipMemcpyAsync(e->slot.p, s.rslot.data(), sizeof(int) * nj, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(e->stop_iter.p, 0, sizeof(int) * nj, st));
+  HIPCHK(hipMemsetAsync(e->stop_reason.p, 0, sizeof(int) * nj, st));
+  HIPCHK(hipMemsetAsync(e->unchanged.p, 0, sizeof(int) * nj, st));
+  HIPCHK(hipMemsetAsync(e->classes.p, 0, sizeof(int) * nj * s.cls_ld, st));   // nmf_mu.c:132 zero start
+  HIPCHK(hipMemsetAsync(e->n_stopped.p, 0, sizeof(int), st));
+  HIPCHK(hipMemsetAsync(e->colact.p, 0, sizeof(int) * cap_cols, st));
+  HIPCHK(hipMemsetAsync(e->W[0].p, 0, sizeof(double) * cap_cols * e->m_pad, st));
+  HIPCHK(hipMemsetAsync(e->H[0].p, 0, sizeof(double) * cap_cols * e->n_pad, st));
+  HIPCHK(hipMemsetAsync(e->W[1].p, 0, sizeof(double) * cap_cols * e->m_pad, st));
+  HIPCHK(hipMemsetAsync(e->H[1].p, 0, sizeof(double) * cap_cols * e->n_pad, st));
   return 0;
 }
 
@@ -834,13 +744,13 @@ int init_from_caller(Sweep& s, const double* W_init, const double* H_init) {
   std::vector<double> hrow;
   for (const RestartInfo& r : s.pk.ri) {
     const int j = s.rslot[r.rid], k = r.k;
-    HCHECK(hipMemcpy2DAsync(e->W[0].as<double>() + (long)r.col0 * e->m_pad, sizeof(double) * e->m_pad,
+    HIPCHK(hipMemcpy2DAsync(e->W[0].as<double>() + (long)r.col0 * e->m_pad, sizeof(double) * e->m_pad,
                             W_init + woff[j], sizeof(double) * m, sizeof(double) * m, k, hipMemcpyHostToDevice, st));
     hrow.assign((size_t)k * n, 0.0);
     transpose(H_init + ho[j], n, k, hrow.data());
-    HCHECK(hipMemcpy2DAsync(e->H[0].as<double>() + (long)r.col0 * e->n_pad, sizeof(double) * e->n_pad, hrow.data(),
+    HIPCHK(hipMemcpy2DAsync(e->H[0].as<double>() + (long)r.col0 * e->n_pad, sizeof(double) * e->n_pad, hrow.data(),
                             sizeof(double) * n, sizeof(double) * n, k, hipMemcpyHostToDevice, st));
-    HCHECK(hipStreamSynchronize(st));   // hrow is reused
+    HIPCHK(hipStreamSynchronize(st));   // hrow is reused
   }
   return 0;
 }
@@ -856,14 +766,14 @@ int init_r_runif(Sweep& s) {
     ij[i] = InitJob{job_seed(s, s.rslot[r.rid]), r.col0, r.k, 0};
   }
   if (e->initjobs.ensure(sizeof(InitJob) * nj)) return -1;
-  HCHECK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
   {
     TimedLaunch tl(e, KID_INIT);
     hipLaunchKernelGGL(k_init_runif, dim3(nj), dim3(NT), 0, st, e->initjobs.as<InitJob>(), e->m, e->n, e->m_pad,
                        e->n_pad, e->W[0].as<double>(), e->H[0].as<double>());
   }
-  HCHECK(hipGetLastError());
-  HCHECK(hipStreamSynchronize(st));   // ij goes out of scope
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));   // ij goes out of scope
   return 0;
 }
 
@@ -899,17 +809,17 @@ int init_glibc(Sweep& s) {
   if (maxch > e->jump_chunks || rchunk != e->jump_rchunk) {
     std::vector<uint32_t> tab = make_jump_table(maxch, rchunk);
     if (e->jump.ensure(sizeof(uint32_t) * tab.size())) return -1;
-    HCHECK(hipMemcpyAsync(e->jump.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, st));
-    HCHECK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(e->jump.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
     e->jump_chunks = maxch;
     e->jump_rchunk = rchunk;
   }
   if (e->initjobs.ensure(sizeof(InitJob) * nj) || e->chunk_job.ensure(sizeof(int) * cj.size()) ||
       e->chunk_idx.ensure(sizeof(int) * ci.size()))
     return -1;
-  HCHECK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
-  HCHECK(hipMemcpyAsync(e->chunk_job.p, cj.data(), sizeof(int) * cj.size(), hipMemcpyHostToDevice, st));
-  HCHECK(hipMemcpyAsync(e->chunk_idx.p, ci.data(), sizeof(int) * ci.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->initjobs.p, ij.data(), sizeof(InitJob) * nj, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->chunk_job.p, cj.data(), sizeof(int) * cj.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->chunk_idx.p, ci.data(), sizeof(int) * ci.size(), hipMemcpyHostToDevice, st));
   const int total_chunks = (int)cj.size();
   {
     TimedLaunch tl(e, KID_INIT);
@@ -918,8 +828,8 @@ int init_glibc(Sweep& s) {
                        m, n, e->m_pad, e->n_pad, s.opts.min_init, s.opts.max_init, e->W[0].as<double>(),
                        e->H[0].as<double>());
   }
-  HCHECK(hipGetLastError());
-  HCHECK(hipStreamSynchronize(st));   // host vectors cj/ci go out of scope
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));   // host vectors cj/ci go out of scope
   return 0;
 }
 
@@ -930,7 +840,7 @@ int archive(Sweep& s, const std::vector<RestartInfo>& list) {
   hipStream_t st = e->st;
   std::vector<MoveJob> mv(list.size());
   for (size_t x = 0; x < list.size(); ++x) mv[x] = {list[x].col0, s.hoff[list[x].rid], list[x].k};
-  HCHECK(hipMemcpyAsync(e->moves.p, mv.data(), sizeof(MoveJob) * mv.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->moves.p, mv.data(), sizeof(MoveJob) * mv.size(), hipMemcpyHostToDevice, st));
   {
     TimedLaunch tl(e, KID_OTHER);
     hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 2), dim3(NT), 0, st, e->moves.as<MoveJob>(),
@@ -939,8 +849,8 @@ int archive(Sweep& s, const std::vector<RestartInfo>& list) {
       hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 16), dim3(NT), 0, st, e->moves.as<MoveJob>(),
                          e->W[s.cur].as<double>(), e->m_pad, e->Wfin.as<double>(), e->m_pad, e->m_pad);
   }
-  HCHECK(hipGetLastError());
-  HCHECK(hipStreamSynchronize(st));   // mv is a host temporary
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));   // mv is a host temporary
   for (const RestartInfo& r : list) s.archived[r.rid] = 1;
   return 0;
 }
@@ -980,16 +890,16 @@ int launch_solo_beside_blocks(Sweep& s) {
     const int kp = nmfc_solo_batch_rank(n, solo[g0].k);
     const long nq = (long)(g1 - g0);
     const long share = std::min<long>(nq, std::max<long>(1, free_cu * nq * wt(kp) / wsum));
-    HCHECK(hipStreamWaitEvent(e->aux[g], e->fork_ev, 0));
+    HIPCHK(hipStreamWaitEvent(e->aux[g], e->fork_ev, 0));
     if (nmfc_solo_batch_launch(e->Acm.as<double>(), e->m_pad, e->m, n, e->W[0].as<double>(), e->m_pad,
                                e->H[0].as<double>(), e->n_pad, e->solojobs.as<SoloJob>() + g0, (int)nq, kp,
                                s.opts.maxiter, s.opts.stop_rule, e->stop_iter.as<int>(), e->stop_reason.as<int>(),
                                (int)share, e->aux[g]))
       return -1;
-    HCHECK(hipEventRecord(e->join_ev[g], e->aux[g]));
+    HIPCHK(hipEventRecord(e->join_ev[g], e->aux[g]));
   }
   // the main stream joins after every launch is enqueued
-  for (int g = 0; g < (int)groups.size(); ++g) HCHECK(hipStreamWaitEvent(e->st, e->join_ev[g], 0));
+  for (int g = 0; g < (int)groups.size(); ++g) HIPCHK(hipStreamWaitEvent(e->st, e->join_ev[g], 0));
   return 0;
 }
 
@@ -1002,23 +912,23 @@ int small_phase(Sweep& s) {
   const std::vector<SoloJob>& solo = s.solo;
   if (!sblocks.empty()) {
     if (e->smallblk.ensure(sizeof(SmallBlock) * sblocks.size())) return -1;
-    HCHECK(hipMemcpyAsync(e->smallblk.p, sblocks.data(), sizeof(SmallBlock) * sblocks.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->smallblk.p, sblocks.data(), sizeof(SmallBlock) * sblocks.size(), hipMemcpyHostToDevice, st));
   }
   if (!solo.empty()) {
     if (e->solojobs.ensure(sizeof(SoloJob) * solo.size())) return -1;
-    HCHECK(hipMemcpyAsync(e->solojobs.p, solo.data(), sizeof(SoloJob) * solo.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->solojobs.p, solo.data(), sizeof(SoloJob) * solo.size(), hipMemcpyHostToDevice, st));
     for (int x = 0; x < 4; ++x) {
-      if (!e->aux[x]) HCHECK(hipStreamCreateWithFlags(&e->aux[x], hipStreamNonBlocking));
-      if (!e->join_ev[x]) HCHECK(hipEventCreateWithFlags(&e->join_ev[x], hipEventDisableTiming));
+      if (!e->aux[x]) HIPCHK(hipStreamCreateWithFlags(&e->aux[x], hipStreamNonBlocking));
+      if (!e->join_ev[x]) HIPCHK(hipEventCreateWithFlags(&e->join_ev[x], hipEventDisableTiming));
     }
-    if (!e->fork_ev) HCHECK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
+    if (!e->fork_ev) HIPCHK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
   }
   {
     TimedLaunch tl(e, KID_SMALL);   // the whole small-shape phase: k_small_mu blocks and the solo launches
     const bool team = use_team(e, (int)sblocks.size());
     // the fork point is recorded BEFORE the block kernel: an event recorded after it would hold the solo launches
     // until the block kernel had finished (round 4: C1 24.7 ms = 9.9 + 14.8 ms serialised)
-    if (!solo.empty() && !team) HCHECK(hipEventRecord(e->fork_ev, st));
+    if (!solo.empty() && !team) HIPCHK(hipEventRecord(e->fork_ev, st));
     if (!sblocks.empty() && launch_small(e, (int)sblocks.size(), s.opts.maxiter, s.opts.stop_rule)) return -1;
     // the solo jobs: after k_small_mu when teams run (a team's workgroups must all be resident at once: nothing else
     // may hold CUs then) or when there are no blocks, else beside it
@@ -1035,9 +945,9 @@ int small_phase(Sweep& s) {
       if (launch_solo_beside_blocks(s)) return -1;
     }
   }
-  HCHECK(hipStreamSynchronize(st));
+  HIPCHK(hipStreamSynchronize(st));
   if (!sblocks.empty() && use_team(e, (int)sblocks.size()) && team_failed(e, (int)sblocks.size())) {
-    set_err("k_team_mu: a team of workgroups could not meet (not co-resident?)");
+    errorf("k_team_mu: a team of workgroups could not meet (not co-resident?)");
     return -1;
   }
   if (e->timing) drain_timing(e);
@@ -1076,14 +986,14 @@ int launch_wta_sk(Sweep& s, bool big, int ng, int* gsplit) {
   hipStream_t st = e->st;
   if (!e->skflag.p) {
     if (e->skfix.ensure(sizeof(double) * SK_FIX * e->ncu) || e->skflag.ensure(sizeof(unsigned) * e->ncu)) return -1;
-    HCHECK(hipMemsetAsync(e->skflag.p, 0, sizeof(unsigned) * e->ncu, st));
+    HIPCHK(hipMemsetAsync(e->skflag.p, 0, sizeof(unsigned) * e->ncu, st));
   }
   ++e->info.wta_sk;
   const long tiles = (long)ng * s.ntj;
   const bool lastsum = e->wta_lastsum && big;
   if (lastsum && e->sktcnt.bytes < sizeof(unsigned) * tiles) {
     if (e->sktcnt.ensure(sizeof(unsigned) * tiles)) return -1;   // fresh tickets: zero
-    HCHECK(hipMemsetAsync(e->sktcnt.p, 0, sizeof(unsigned) * tiles, st));
+    HIPCHK(hipMemsetAsync(e->sktcnt.p, 0, sizeof(unsigned) * tiles, st));
   }
   const SkArgs a{e->W[s.cur].as<double>(), e->Ablk.as<double>(), e->m_pad, ng, s.ntj, e->kchunk,
                  e->prb.as<int>(), e->pre.as<int>(), e->rinfo.as<RestartInfo>(), e->colinfo.as<ColInfo>(),
@@ -1269,7 +1179,7 @@ int enqueue_iteration(Sweep& s, const ChunkPlan& cp, int iter) {
   // STOP_TOLX (even iterations > 1): snapshot W before its update, test after it
   const bool tol_check = s.tolx && iter > 1 && iter % 2 == 0;
   if (tol_check)
-    HCHECK(hipMemcpyAsync(e->Wsnap.p, e->W[s.cur].p, sizeof(double) * (size_t)s.pk.npanels * PANEL * e->m_pad,
+    HIPCHK(hipMemcpyAsync(e->Wsnap.p, e->W[s.cur].p, sizeof(double) * (size_t)s.pk.npanels * PANEL * e->m_pad,
                           hipMemcpyDeviceToDevice, e->st));
   {
     TimedLaunch tl(e, KID_AHTW, sample);
@@ -1289,10 +1199,10 @@ int enqueue_chunk(Sweep& s) {
   const ChunkPlan cp = plan_chunk(s);
   for (int c = 1; c <= chunk; ++c)
     if (enqueue_iteration(s, cp, s.it + c)) return -1;
-  HCHECK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   s.it += chunk;
-  HCHECK(hipMemcpyAsync(&e->h_stopped[s.polls & 1], e->n_stopped.p, sizeof(int), hipMemcpyDeviceToHost, e->st));
-  HCHECK(hipEventRecord(s.pe.ev[s.polls & 1], e->st));
+  HIPCHK(hipMemcpyAsync(&e->h_stopped.as<int>()[s.polls & 1], e->n_stopped.p, sizeof(int), hipMemcpyDeviceToHost, e->st));
+  HIPCHK(hipEventRecord(s.pe.ev[s.polls & 1], e->st));
   ++s.polls;
   return 0;
 }
@@ -1301,8 +1211,8 @@ int enqueue_chunk(Sweep& s) {
 int consume_polls(Sweep& s, int* stopped, bool* done) {
   const int target = (s.it < s.opts.maxiter) ? s.polls - 1 : s.polls;
   while (s.checked < target) {
-    HCHECK(hipEventSynchronize(s.pe.ev[s.checked & 1]));
-    *stopped = s.e->h_stopped[s.checked & 1];
+    HIPCHK(hipEventSynchronize(s.pe.ev[s.checked & 1]));
+    *stopped = s.e->h_stopped.as<int>()[s.checked & 1];
     if (*stopped >= s.nj) *done = true;
     ++s.checked;
   }
@@ -1315,10 +1225,10 @@ int repack(Sweep& s, int stopped) {
   nmfc_engine* e = s.e;
   hipStream_t st = e->st;
   const int nj = s.nj;
-  HCHECK(hipStreamSynchronize(st));
+  HIPCHK(hipStreamSynchronize(st));
   if (e->timing) drain_timing(e);
   s.checked = s.polls;   // every poll is now complete
-  HCHECK(hipMemcpy(s.si.data(), e->stop_iter.p, sizeof(int) * nj, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(s.si.data(), e->stop_iter.p, sizeof(int) * nj, hipMemcpyDeviceToHost));
   std::vector<RestartInfo> gone, live;
   for (const RestartInfo& r : s.pk.ri) {
     if (!s.si[r.rid])
@@ -1340,7 +1250,7 @@ int repack(Sweep& s, int stopped) {
   std::vector<MoveJob> mv(np.ri.size());
   for (size_t x = 0; x < np.ri.size(); ++x) mv[x] = {old_col[np.ri[x].rid], np.ri[x].col0, np.ri[x].k};
   if (!mv.empty()) {
-    HCHECK(hipMemcpyAsync(e->moves.p, mv.data(), sizeof(MoveJob) * mv.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->moves.p, mv.data(), sizeof(MoveJob) * mv.size(), hipMemcpyHostToDevice, st));
     {
       TimedLaunch tl(e, KID_OTHER);
       hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 16), dim3(NT), 0, st, e->moves.as<MoveJob>(),
@@ -1348,12 +1258,12 @@ int repack(Sweep& s, int stopped) {
       hipLaunchKernelGGL(k_move_rows, dim3((unsigned)mv.size(), 2), dim3(NT), 0, st, e->moves.as<MoveJob>(),
                          e->H[s.cur].as<double>(), e->n_pad, e->H[s.cur ^ 1].as<double>(), e->n_pad, e->n_pad);
     }
-    HCHECK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   s.cur ^= 1;
   s.pk = np;
   if (upload_packing(e, s.pk)) return -1;
-  HCHECK(hipStreamSynchronize(st));   // mv / pk host data uploaded
+  HIPCHK(hipStreamSynchronize(st));   // mv / pk host data uploaded
   s.nact = (int)s.pk.ri.size();
   s.stopped_at_pack = nj - s.nact;
   ++e->repacks;
@@ -1364,8 +1274,8 @@ int repack(Sweep& s, int stopped) {
 // The MFMA path's poll / repack loop: chunks of check_every iterations, one always in flight behind the poll read.
 int mfma_loop(Sweep& s) {
   nmfc_engine* e = s.e;
-  HCHECK(hipEventCreateWithFlags(&s.pe.ev[0], hipEventDisableTiming));
-  HCHECK(hipEventCreateWithFlags(&s.pe.ev[1], hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&s.pe.ev[0], hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&s.pe.ev[1], hipEventDisableTiming));
   for (;;) {
     if (s.it < s.opts.maxiter && enqueue_chunk(s)) return -1;
     int stopped = 0;
@@ -1392,13 +1302,13 @@ int residual_pass(Sweep& s) {
   const int nst = (e->n + RES_ST - 1) / RES_ST, ntiles = (e->m + RES_GT - 1) / RES_GT * nst;
   const int ngroups = (nj + RES_JG - 1) / RES_JG;
   if (ngroups > 65535) {
-    set_err("nmfc_engine_run: residuals of %d jobs exceed the residual pass's grid", nj);
+    errorf("nmfc_engine_run: residuals of %d jobs exceed the residual pass's grid", nj);
     return -1;
   }
   if (e->ssq.ensure(sizeof(double) * nj) || e->respart.ensure(sizeof(double) * (size_t)nj * ntiles)) return -1;
   s.fin.resize(nj);
   for (int rid = 0; rid < nj; ++rid) s.fin[rid] = {s.hoff[rid], s.all[rid].k, rid, s.all[rid].sq_off};
-  HCHECK(hipMemcpyAsync(e->finfo.p, s.fin.data(), sizeof(RestartInfo) * nj, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->finfo.p, s.fin.data(), sizeof(RestartInfo) * nj, hipMemcpyHostToDevice, st));
   {
     TimedLaunch tl(e, KID_RESID);
     hipLaunchKernelGGL(k_resid, dim3(ntiles, ngroups), dim3(NT), 0, st, e->finfo.as<RestartInfo>(), nj,
@@ -1407,9 +1317,9 @@ int residual_pass(Sweep& s) {
     hipLaunchKernelGGL(k_resid_sum, dim3(nj), dim3(64), 0, st, e->respart.as<double>(), ntiles, e->slot.as<int>(),
                        e->ssq.as<double>());
   }
-  HCHECK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   e->h_ssq.assign(nj, 0.0);
-  HCHECK(hipMemcpyAsync(e->h_ssq.data(), e->ssq.p, sizeof(double) * nj, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(e->h_ssq.data(), e->ssq.p, sizeof(double) * nj, hipMemcpyDeviceToHost, st));
   // accounting (one launch pair): (2k + 3) m n lane operations per job; A once per group of RES_JG restarts, a job's W
   // once per sample tile and H once per gene tile, the partials written and read (algorithmic: each operand once)
   double fl = 0, bw = 0, bh = 0;
@@ -1434,13 +1344,13 @@ int labels_counts_consensus(Sweep& s, nmfc_result* out) {
   const int n = e->n, nj = s.nj, nk = s.nk;
   std::vector<RestartInfo> fin(nj);
   for (int rid = 0; rid < nj; ++rid) fin[rid] = {s.hoff[rid], s.all[rid].k, rid, s.all[rid].sq_off};
-  HCHECK(hipMemcpyAsync(e->finfo.p, fin.data(), sizeof(RestartInfo) * nj, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->finfo.p, fin.data(), sizeof(RestartInfo) * nj, hipMemcpyHostToDevice, st));
   {
     TimedLaunch tl(e, KID_LABELS);
     hipLaunchKernelGGL(k_labels, dim3((n + NT - 1) / NT, nj), dim3(NT), 0, st, e->finfo.as<RestartInfo>(),
                        e->slot.as<int>(), e->Hfin.as<double>(), e->n_pad, n, s.opts.label_rule, e->labels.as<int32_t>());
   }
-  HCHECK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   std::vector<int> gb(nk + 1, 0), gl;
   for (int g = 0; g < nk; ++g) {
     gb[g] = (int)gl.size();
@@ -1452,8 +1362,8 @@ int labels_counts_consensus(Sweep& s, nmfc_result* out) {
   if (out && (out->counts || out->consensus)) {
     if (e->grp_begin.ensure(sizeof(int) * (nk + 1)) || e->grp_list.ensure(sizeof(int) * std::max<size_t>(gl.size(), 1)))
       return -1;
-    HCHECK(hipMemcpyAsync(e->grp_begin.p, gb.data(), sizeof(int) * (nk + 1), hipMemcpyHostToDevice, st));
-    if (!gl.empty()) HCHECK(hipMemcpyAsync(e->grp_list.p, gl.data(), sizeof(int) * gl.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->grp_begin.p, gb.data(), sizeof(int) * (nk + 1), hipMemcpyHostToDevice, st));
+    if (!gl.empty()) HIPCHK(hipMemcpyAsync(e->grp_list.p, gl.data(), sizeof(int) * gl.size(), hipMemcpyHostToDevice, st));
     int32_t* dcounts;
     if (out->counts && out->counts_on_device) {
       dcounts = out->counts;
@@ -1466,22 +1376,22 @@ int labels_counts_consensus(Sweep& s, nmfc_result* out) {
       hipLaunchKernelGGL(k_counts, dim3((n + CNT_T - 1) / CNT_T, (n + CNT_T - 1) / CNT_T, nk), dim3(NT), 0, st, e->labels.as<int32_t>(),
                          e->grp_begin.as<int>(), e->grp_list.as<int>(), n, dcounts);
     }
-    HCHECK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     if (out->consensus) {
       if (e->cons_tmp.ensure(sizeof(double) * cnt_len)) return -1;
       hipLaunchKernelGGL(k_divide, dim3((unsigned)((cnt_len + NT - 1) / NT)), dim3(NT), 0, st, dcounts, (double)s.R,
                          (long)cnt_len, e->cons_tmp.as<double>());
-      HCHECK(hipGetLastError());
-      HCHECK(hipMemcpyAsync(out->consensus, e->cons_tmp.p, sizeof(double) * cnt_len, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(out->consensus, e->cons_tmp.p, sizeof(double) * cnt_len, hipMemcpyDeviceToHost, st));
     }
     if (out->counts && !out->counts_on_device)
-      HCHECK(hipMemcpyAsync(out->counts, dcounts, sizeof(int32_t) * cnt_len, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(out->counts, dcounts, sizeof(int32_t) * cnt_len, hipMemcpyDeviceToHost, st));
   }
-  HCHECK(hipMemcpyAsync(s.si.data(), e->stop_iter.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-  HCHECK(hipMemcpyAsync(s.sr.data(), e->stop_reason.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(s.si.data(), e->stop_iter.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(s.sr.data(), e->stop_reason.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
   if (out && out->labels)
-    HCHECK(hipMemcpyAsync(out->labels, e->labels.p, sizeof(int32_t) * (size_t)nj * n, hipMemcpyDeviceToHost, st));
-  HCHECK(hipStreamSynchronize(st));   // fin, gb, gl uploaded; si, sr and the caller's arrays filled
+    HIPCHK(hipMemcpyAsync(out->labels, e->labels.p, sizeof(int32_t) * (size_t)nj * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));   // fin, gb, gl uploaded; si, sr and the caller's arrays filled
   if (e->timing) drain_timing(e);
   return 0;
 }
@@ -1555,17 +1465,17 @@ int download_factors(Sweep& s, nmfc_result* out) {
   for (int rid = 0; rid < s.nj; ++rid) {
     const int j = s.rslot[rid], k = s.all[rid].k;
     if (out->W)
-      HCHECK(hipMemcpy2DAsync(out->W + woff[j], sizeof(double) * m, e->Wfin.as<double>() + (long)s.hoff[rid] * e->m_pad,
+      HIPCHK(hipMemcpy2DAsync(out->W + woff[j], sizeof(double) * m, e->Wfin.as<double>() + (long)s.hoff[rid] * e->m_pad,
                               sizeof(double) * e->m_pad, sizeof(double) * m, k, hipMemcpyDeviceToHost, st));
     if (out->H) {
       hrow.assign((size_t)k * n, 0.0);
-      HCHECK(hipMemcpy2DAsync(hrow.data(), sizeof(double) * n, e->Hfin.as<double>() + (long)s.hoff[rid] * e->n_pad,
+      HIPCHK(hipMemcpy2DAsync(hrow.data(), sizeof(double) * n, e->Hfin.as<double>() + (long)s.hoff[rid] * e->n_pad,
                               sizeof(double) * e->n_pad, sizeof(double) * n, k, hipMemcpyDeviceToHost, st));
-      HCHECK(hipStreamSynchronize(st));
+      HIPCHK(hipStreamSynchronize(st));
       transpose(hrow.data(), k, n, out->H + ho[j]);
     }
   }
-  HCHECK(hipStreamSynchronize(st));
+  HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -1596,12 +1506,12 @@ void nmfc_default_opts(nmfc_sweep_opts* o) {
 
 nmfc_engine* nmfc_engine_create(int device, const double* A, int m, int n, int a_on_device) {
   if (!A || m <= 0 || n <= 0) {
-    set_err("nmfc_engine_create: bad arguments (A=%p m=%d n=%d)", (const void*)A, m, n);
+    errorf("nmfc_engine_create: bad arguments (A=%p m=%d n=%d)", (const void*)A, m, n);
     return nullptr;
   }
   nmfc_engine* e = new nmfc_engine();
   auto fail = [&](const char* what, hipError_t err) -> nmfc_engine* {
-    set_err("nmfc_engine_create: %s: %s", what, hipGetErrorString(err));
+    nmfc_host::hip_fail("nmfc_engine_create", what, err);
     nmfc_engine_destroy(e);
     return nullptr;
   };
@@ -1636,7 +1546,10 @@ nmfc_engine* nmfc_engine_create(int device, const double* A, int m, int n, int a
     e->force_ahtw = v == "128" ? 0 : v == "64" ? 1 : -1;
   }
   if ((err = hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", err);
-  if ((err = hipHostMalloc((void**)&e->h_stopped, 2 * sizeof(int), 0)) != hipSuccess) return fail("hipHostMalloc", err);
+  if (e->h_stopped.ensure(2 * sizeof(int))) {
+    nmfc_engine_destroy(e);
+    return nullptr;
+  }
   e->m = m;
   e->n = n;
   e->m_pad = round_up(m, GT);          // gene tiles of A h^T and Gram partials
@@ -1681,7 +1594,6 @@ nmfc_engine* nmfc_engine_create(int device, const double* A, int m, int n, int a
                      e->st, dA, (long)m, m, n, e->n_cols_pad, e->Ablk.as<double>());
   if ((err = hipGetLastError()) != hipSuccess) return fail("k_layout_a", err);
   if ((err = hipStreamSynchronize(e->st)) != hipSuccess) return fail("sync", err);
-  tmp.release();
   return e;
 }
 
@@ -1689,16 +1601,14 @@ void nmfc_engine_destroy(nmfc_engine* e) {
   if (!e) return;
   if (e->st) (void)hipStreamSynchronize(e->st);
   drain_timing(e);
-  for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
+  e->timer.destroy_events();
   for (int x = 0; x < 4; ++x) {
     if (e->aux[x]) (void)hipStreamDestroy(e->aux[x]);
     if (e->join_ev[x]) (void)hipEventDestroy(e->join_ev[x]);
   }
   if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
-  if (e->h_stopped) (void)hipHostFree(e->h_stopped);
-  if (e->mu1_host) (void)hipHostFree(e->mu1_host);
   if (e->st) (void)hipStreamDestroy(e->st);
-  delete e;   // every DevBuf member frees itself
+  delete e;   // every DevBuf / PinBuf member frees itself
 }
 
 int nmfc_engine_device(const nmfc_engine* e) { return e ? e->dev : -1; }
@@ -1720,11 +1630,11 @@ void nmfc_engine_set_residuals(nmfc_engine* e, int enable) {
 
 int nmfc_engine_set_euclid(nmfc_engine* e, int enable, int stopconv, int stopfreq) {
   if (!e) {
-    set_err("nmfc_engine_set_euclid: no engine");
+    errorf("nmfc_engine_set_euclid: no engine");
     return -1;
   }
   if (enable && (stopconv < 1 || stopfreq < 1)) {
-    set_err("nmfc_engine_set_euclid: stopconv = %d and stopfreq = %d must both be >= 1", stopconv, stopfreq);
+    errorf("nmfc_engine_set_euclid: stopconv = %d and stopfreq = %d must both be >= 1", stopconv, stopfreq);
     return -1;
   }
   e->euclid = enable != 0;
@@ -1741,11 +1651,11 @@ double resid_norm(const nmfc_engine* e, int slot) { return sqrt(e->h_ssq[slot]) 
 
 int resid_ready(const nmfc_engine* e, const char* who) {
   if (!e) {
-    set_err("%s: no engine", who);
+    errorf("%s: no engine", who);
     return -1;
   }
   if (!e->resid_valid) {
-    set_err("%s: the last run on this engine had residuals disabled or failed (nmfc_engine_set_residuals)", who);
+    errorf("%s: the last run on this engine had residuals disabled or failed (nmfc_engine_set_residuals)", who);
     return -1;
   }
   return 0;
@@ -1755,7 +1665,7 @@ int resid_ready(const nmfc_engine* e, const char* who) {
 int nmfc_engine_residuals(nmfc_engine* e, double* dnorm_out) {
   if (resid_ready(e, "nmfc_engine_residuals")) return -1;
   if (!dnorm_out) {
-    set_err("nmfc_engine_residuals: dnorm_out is NULL");
+    errorf("nmfc_engine_residuals: dnorm_out is NULL");
     return -1;
   }
   const int nj = (int)e->h_ssq.size();
@@ -1776,7 +1686,7 @@ int nmfc_engine_best(nmfc_engine* e, int32_t* best_job_out, double* best_dnorm_o
       bd[g] = d;
     }
   }
-  if (W_out || H_out) HCHECK(hipSetDevice(e->dev));
+  if (W_out || H_out) HIPCHK(hipSetDevice(e->dev));
   std::vector<double> hrow;
   long woff = 0, hoff = 0;
   for (int g = 0; g < nk; ++g) {
@@ -1784,19 +1694,19 @@ int nmfc_engine_best(nmfc_engine* e, int32_t* best_job_out, double* best_dnorm_o
     if (best_job_out) best_job_out[g] = j < 0 ? -1 : (int32_t)(e->last_jb + j);
     if (best_dnorm_out) best_dnorm_out[g] = bd[g];
     if (j >= 0 && W_out)
-      HCHECK(hipMemcpy2DAsync(W_out + woff, sizeof(double) * m, e->Wfin.as<double>() + (long)e->last_row[j] * e->m_pad,
+      HIPCHK(hipMemcpy2DAsync(W_out + woff, sizeof(double) * m, e->Wfin.as<double>() + (long)e->last_row[j] * e->m_pad,
                               sizeof(double) * e->m_pad, sizeof(double) * m, k, hipMemcpyDeviceToHost, e->st));
     if (j >= 0 && H_out) {
       hrow.assign((size_t)k * n, 0.0);
-      HCHECK(hipMemcpy2DAsync(hrow.data(), sizeof(double) * n, e->Hfin.as<double>() + (long)e->last_row[j] * e->n_pad,
+      HIPCHK(hipMemcpy2DAsync(hrow.data(), sizeof(double) * n, e->Hfin.as<double>() + (long)e->last_row[j] * e->n_pad,
                               sizeof(double) * e->n_pad, sizeof(double) * n, k, hipMemcpyDeviceToHost, e->st));
-      HCHECK(hipStreamSynchronize(e->st));
+      HIPCHK(hipStreamSynchronize(e->st));
       transpose(hrow.data(), k, n, H_out + hoff);
     }
     woff += (long)m * k;
     hoff += (long)k * n;
   }
-  HCHECK(hipStreamSynchronize(e->st));
+  HIPCHK(hipStreamSynchronize(e->st));
   return nk;
 }
 
@@ -1857,7 +1767,7 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
   // ---- iterate ----
   const auto t_iter0 = clk::now();
   if (s.small ? small_phase(s) : mfma_loop(s)) return -1;
-  HCHECK(hipStreamSynchronize(e->st));
+  HIPCHK(hipStreamSynchronize(e->st));
   if (e->timing) drain_timing(e);
   e->info.polls = s.polls;
   e->info.iterations_enqueued = s.it;
@@ -1896,28 +1806,24 @@ int nmfc_engine_mu1(nmfc_engine* e, int k, int maxiter, int stop_rule, const dou
                     double* W_out, double* H_out, int* iters, int* early) {
   if (!e || !W0 || !H0 || !W_out || !H_out || maxiter < 0 || k < 1 || k > 16 || k > e->m || k > e->n ||
       !nmfc_mu_stop_rule_ok(stop_rule)) {
-    set_err("nmfc_engine_mu1: bad arguments");
+    errorf("nmfc_engine_mu1: bad arguments");
     return -1;
   }
   const int m = e->m, n = e->n;
   const int jb = (n + 15) / 16;
   const int P = (int)(e->m_pad / TEAM_ROWS);
   if (!e->small_ok || e->small_kernel == 2 || n > 64 || P > TEAM_PMAX) {
-    set_err("nmfc_engine_mu1: shape %d x %d is not a team shape (m rounded up to 128 <= %d, n <= 64)", m, n,
-            TEAM_ROWS * TEAM_PMAX);
+    errorf("nmfc_engine_mu1: shape %d x %d is not a team shape (m rounded up to 128 <= %d, n <= 64)", m, n,
+           TEAM_ROWS * TEAM_PMAX);
     return -1;
   }
-  HCHECK(hipSetDevice(e->dev));
+  HIPCHK(hipSetDevice(e->dev));
   const long mp = e->m_pad, np = e->n_pad;
   const size_t off_stop = 256, off_w = 512, off_h = off_w + sizeof(double) * 16 * mp;
   const size_t total = off_h + sizeof(double) * 16 * np;
-  if (e->mu1_host_bytes < total) {
-    if (e->mu1_host) (void)hipHostFree(e->mu1_host);
-    e->mu1_host = nullptr;
-    e->mu1_host_bytes = 0;
-    HCHECK(hipHostMalloc((void**)&e->mu1_host, total, 0));
-    memset(e->mu1_host, 0, total);
-    e->mu1_host_bytes = total;
+  if (e->mu1_host.bytes < total) {
+    if (e->mu1_host.ensure(total)) return -1;
+    memset(e->mu1_host.p, 0, total);
     e->mu1_kprev = 16;
   }
   if (e->mu1_dev.ensure(total) || e->mu1_G.ensure(sizeof(double) * 2 * TEAM_PMAX * 16 * 16 * jb) ||
@@ -1926,10 +1832,10 @@ int nmfc_engine_mu1(nmfc_engine* e, int k, int maxiter, int stop_rule, const dou
   if (!e->mu1_flag.p) e->mu1_base = -1;
   if (e->mu1_flag.ensure(sizeof(unsigned) * TEAM_PMAX)) return -1;
   if (e->mu1_base < 0 || e->mu1_base > (1 << 30)) {
-    HCHECK(hipMemsetAsync(e->mu1_flag.p, 0, sizeof(unsigned) * TEAM_PMAX, e->st));
+    HIPCHK(hipMemsetAsync(e->mu1_flag.p, 0, sizeof(unsigned) * TEAM_PMAX, e->st));
     e->mu1_base = 0;
   }
-  char* hb = e->mu1_host;
+  char* hb = e->mu1_host.as<char>();
   SmallBlock blk{};
   blk.col0 = 0;
   blk.nr = 1;
@@ -1950,19 +1856,19 @@ int nmfc_engine_mu1(nmfc_engine* e, int k, int maxiter, int stop_rule, const dou
   }
   e->mu1_kprev = k;
   char* db = static_cast<char*>(e->mu1_dev.p);
-  HCHECK(hipMemcpyAsync(db, hb, total, hipMemcpyHostToDevice, e->st));
+  HIPCHK(hipMemcpyAsync(db, hb, total, hipMemcpyHostToDevice, e->st));
   auto kern = jb == 1 ? k_team_mu<1> : jb == 2 ? k_team_mu<2> : jb == 3 ? k_team_mu<3> : k_team_mu<4>;
   int* dstop = reinterpret_cast<int*>(db + off_stop);
   hipLaunchKernelGGL(kern, dim3(P), dim3(256), 0, e->st, reinterpret_cast<const SmallBlock*>(db), 1, P, e->Acm.as<double>(),
                      mp, n, np, reinterpret_cast<double*>(db + off_w), reinterpret_cast<double*>(db + off_h), maxiter,
                      stop_rule, dstop, dstop + 1, e->mu1_G.as<double>(), e->mu1_SW.as<double>(),
                      e->mu1_flag.as<unsigned>(), (unsigned)e->mu1_base, dstop + 2, nullptr);
-  HCHECK(hipGetLastError());
-  HCHECK(hipMemcpyAsync(hb + off_stop, db + off_stop, total - off_stop, hipMemcpyDeviceToHost, e->st));
-  HCHECK(hipStreamSynchronize(e->st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(hb + off_stop, db + off_stop, total - off_stop, hipMemcpyDeviceToHost, e->st));
+  HIPCHK(hipStreamSynchronize(e->st));
   if (hstop[2]) {
     e->mu1_base = -1;
-    set_err("k_team_mu: the team could not meet (not co-resident?)");
+    errorf("k_team_mu: the team could not meet (not co-resident?)");
     return -1;
   }
   const int it = maxiter == 0 ? 0 : hstop[0];
@@ -1978,7 +1884,7 @@ int nmfc_engine_mu1(nmfc_engine* e, int k, int maxiter, int stop_rule, const dou
 int nmfc_consensus(const double* Hs, int k, int n, int R, int label_rule, int32_t* labels, int32_t* counts,
                    double* consensus) {
   if (!Hs || k < 1 || n < 1 || R < 1 || label_rule < 0 || label_rule > 1) {
-    set_err("nmfc_consensus: bad arguments");
+    errorf("nmfc_consensus: bad arguments");
     return -1;
   }
   std::vector<double> hrows((size_t)R * k * n);
@@ -1996,23 +1902,23 @@ int nmfc_consensus(const double* Hs, int k, int n, int R, int label_rule, int32_
       dgb.ensure(sizeof(int) * 2) || dlab.ensure(sizeof(int32_t) * (size_t)R * n) ||
       dcnt.ensure(sizeof(int32_t) * (size_t)n * n) || dcons.ensure(sizeof(double) * (size_t)n * n))
     return -1;
-  HCHECK(hipMemcpy(dH.p, hrows.data(), sizeof(double) * hrows.size(), hipMemcpyHostToDevice));
-  HCHECK(hipMemcpy(dri.p, ri.data(), sizeof(RestartInfo) * R, hipMemcpyHostToDevice));
-  HCHECK(hipMemcpy(dslot.p, slot.data(), sizeof(int) * R, hipMemcpyHostToDevice));
-  HCHECK(hipMemcpy(dgb.p, gb.data(), sizeof(int) * 2, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dH.p, hrows.data(), sizeof(double) * hrows.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dri.p, ri.data(), sizeof(RestartInfo) * R, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dslot.p, slot.data(), sizeof(int) * R, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dgb.p, gb.data(), sizeof(int) * 2, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_labels, dim3((n + NT - 1) / NT, R), dim3(NT), 0, 0, dri.as<RestartInfo>(), dslot.as<int>(),
                      dH.as<double>(), (long)n, n, label_rule, dlab.as<int32_t>());
-  HCHECK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_counts, dim3((n + CNT_T - 1) / CNT_T, (n + CNT_T - 1) / CNT_T, 1), dim3(NT), 0, 0, dlab.as<int32_t>(), dgb.as<int>(),
                      dslot.as<int>(), n, dcnt.as<int32_t>());
-  HCHECK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_divide, dim3((unsigned)(((size_t)n * n + NT - 1) / NT)), dim3(NT), 0, 0, dcnt.as<int32_t>(),
                      (double)R, (long)n * n, dcons.as<double>());
-  HCHECK(hipGetLastError());
-  if (labels) HCHECK(hipMemcpy(labels, dlab.p, sizeof(int32_t) * (size_t)R * n, hipMemcpyDeviceToHost));
-  if (counts) HCHECK(hipMemcpy(counts, dcnt.p, sizeof(int32_t) * (size_t)n * n, hipMemcpyDeviceToHost));
-  if (consensus) HCHECK(hipMemcpy(consensus, dcons.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
-  HCHECK(hipDeviceSynchronize());
+  HIPCHK(hipGetLastError());
+  if (labels) HIPCHK(hipMemcpy(labels, dlab.p, sizeof(int32_t) * (size_t)R * n, hipMemcpyDeviceToHost));
+  if (counts) HIPCHK(hipMemcpy(counts, dcnt.p, sizeof(int32_t) * (size_t)n * n, hipMemcpyDeviceToHost));
+  if (consensus) HIPCHK(hipMemcpy(consensus, dcons.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipDeviceSynchronize());
   return 0;
 }
 

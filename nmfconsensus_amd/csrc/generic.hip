@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/nmfc.h"
+#include "nmfc_host.hpp"
 #include "nmfc_internal.hpp"
 #include "nmfc_kernels.hpp"
 
@@ -104,104 +105,37 @@ __global__ __launch_bounds__(GB) void k_gen_check(int iter, int maxiter, int sto
   }
 }
 
-struct GenCache {   // device copy of the last A (compared byte for byte) and work buffers
-  std::vector<double> a;
-  int m = 0, n = 0;
-  double* dA = nullptr;
-  double* work = nullptr;
-  size_t work_bytes = 0;
-  int* state = nullptr;
-  int* cls = nullptr;   // the stability check's classes (n of them)
-  int cls_n = 0;
+struct GenCache : nmfc_host::MuCacheBase {   // device copy of the last A and work buffers
+  nmfc_host::DevBuf dA, work, state;
+  nmfc_host::DevBuf cls;   // the stability check's classes (n of them)
   hipStream_t st = nullptr;
-  int dev = -1;         // the HIP device every resource above lives on
-};
-std::mutex g_lock;
-GenCache g;
-
-void cache_drop() {   // g_lock held
-  if (g.st) (void)hipStreamSynchronize(g.st);
-  if (g.dA) (void)hipFree(g.dA);
-  if (g.work) (void)hipFree(g.work);
-  if (g.state) (void)hipFree(g.state);
-  if (g.cls) (void)hipFree(g.cls);
-  if (g.st) (void)hipStreamDestroy(g.st);
-  g.a.clear();
-  g.a.shrink_to_fit();
-  g.dA = g.work = nullptr;
-  g.state = g.cls = nullptr;
-  g.st = nullptr;
-  g.work_bytes = 0;
-  g.cls_n = 0;
-  g.m = g.n = 0;
-  g.dev = -1;
-}
-
-int mu_generic_call(const double* A, int m, int n, int k, int maxiter, int stop_rule, double* W, double* H, int* iters,
-                    int* early);
-
-int fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "nmfc_mu_generic: %s: %s", what, hipGetErrorString(e));
-  nmfc_set_error(buf);
-  return -1;
-}
-
-}  // namespace
-
-#define GCHECK(x)                          \
-  do {                                     \
-    hipError_t e_ = (x);                   \
-    if (e_ != hipSuccess) return fail(#x, e_); \
-  } while (0)
-
-extern "C" int nmfc_mu_generic(const double* A, int m, int n, int k, int maxiter, int stop_rule, double* W, double* H,
-                               int* iters, int* early) {
-  if (!A || !W || !H || m < 1 || n < 1 || k < 1 || k > m || k > n || maxiter < 0 ||
-      !nmfc_mu_stop_rule_ok(stop_rule)) {
-    nmfc_set_error("nmfc_mu_generic: bad arguments");
-    return -1;
+  void drop() {   // lock held
+    if (st) (void)hipStreamSynchronize(st);
+    for (nmfc_host::DevBuf* b : {&dA, &work, &state, &cls}) b->release();
+    if (st) (void)hipStreamDestroy(st);
+    st = nullptr;
+    drop_key();
   }
-  std::lock_guard<std::mutex> lock(g_lock);
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return fail("hipGetDevice", hipErrorInvalidDevice);
-  if (g.dev >= 0 && g.dev != dev) cache_drop();
-  const int rc = mu_generic_call(A, m, n, k, maxiter, stop_rule, W, H, iters, early);
-  // a failed call may leave a half-done upload behind: nothing of it is reused; NMFC_NMF_MU_CACHE=0 keeps nothing
-  const char* env = getenv("NMFC_NMF_MU_CACHE");
-  if (rc != 0 || (env && atoi(env) == 0))
-    cache_drop();
-  else
-    g.dev = dev;
-  return rc;
-}
+};
+GenCache& g = *new GenCache;   // never destroyed (nmfc_host.hpp, process exit)
 
-namespace {
+constexpr char WHO[] = "nmfc_mu_generic";   // the entry point HIPCHK reports under
+
 int mu_generic_call(const double* A, int m, int n, int k, int maxiter, int stop_rule, double* W, double* H, int* iters,
                     int* early) {
   const size_t la = (size_t)m * n;
-  if (!g.st) GCHECK(hipStreamCreateWithFlags(&g.st, hipStreamNonBlocking));
-  if (!(g.dA && g.m == m && g.n == n && memcmp(g.a.data(), A, la * sizeof(double)) == 0)) {
-    if (g.dA) (void)hipFree(g.dA);
-    g.dA = nullptr;
-    g.a.assign(A, A + la);
-    g.m = m;
-    g.n = n;
-    GCHECK(hipMalloc(&g.dA, la * sizeof(double)));
-    GCHECK(hipMemcpyAsync(g.dA, A, la * sizeof(double), hipMemcpyHostToDevice, g.st));
+  if (!g.st) HIPCHK(hipStreamCreateWithFlags(&g.st, hipStreamNonBlocking), WHO);
+  if (!(g.dA.p && g.key.same(A, m, n))) {
+    g.key.set(A, m, n);
+    if (g.dA.ensure(la * sizeof(double))) return -1;
+    HIPCHK(hipMemcpyAsync(g.dA.p, A, la * sizeof(double), hipMemcpyHostToDevice, g.st), WHO);
   }
   // work: W, H, numerh / hden (k x n), wtw / hht (k x k), numerw / wden (m x k)
   const size_t lw = (size_t)m * k, lh = (size_t)k * n, lk = (size_t)k * k;
-  const size_t need = sizeof(double) * (3 * lw + 3 * lh + 2 * lk);
-  if (g.work_bytes < need) {
-    if (g.work) (void)hipFree(g.work);
-    g.work = nullptr;
-    g.work_bytes = 0;
-    GCHECK(hipMalloc(&g.work, need));
-    g.work_bytes = need;
-  }
-  if (!g.state) GCHECK(hipMalloc(&g.state, sizeof(int) * 8));
-  double* dW = g.work;
+  if (g.work.ensure(sizeof(double) * (3 * lw + 3 * lh + 2 * lk)) || g.state.ensure(sizeof(int) * 8) ||
+      g.cls.ensure(sizeof(int) * (size_t)n))
+    return -1;
+  double* dW = g.work.as<double>();
   double* dH = dW + lw;
   double* numw = dH + lh;
   double* denw = numw + lw;
@@ -209,20 +143,14 @@ int mu_generic_call(const double* A, int m, int n, int k, int maxiter, int stop_
   double* denh = numh + lh;
   double* wtw = denh + lh;
   double* hht = wtw + lk;
-  if (g.cls_n < n) {
-    if (g.cls) (void)hipFree(g.cls);
-    g.cls = nullptr;
-    g.cls_n = 0;
-    GCHECK(hipMalloc(&g.cls, sizeof(int) * (size_t)n));
-    g.cls_n = n;
-  }
-  int* cls = g.cls;
-  GCHECK(hipMemsetAsync(cls, 0, sizeof(int) * (size_t)n, g.st));   // nmf_mu.c:132
-  GCHECK(hipMemsetAsync(g.state, 0, sizeof(int) * 8, g.st));
-  GCHECK(hipMemcpyAsync(dW, W, lw * sizeof(double), hipMemcpyHostToDevice, g.st));
-  GCHECK(hipMemcpyAsync(dH, H, lh * sizeof(double), hipMemcpyHostToDevice, g.st));
+  int* cls = g.cls.as<int>();
+  int* state = g.state.as<int>();
+  HIPCHK(hipMemsetAsync(cls, 0, sizeof(int) * (size_t)n, g.st), WHO);   // nmf_mu.c:132
+  HIPCHK(hipMemsetAsync(state, 0, sizeof(int) * 8, g.st), WHO);
+  HIPCHK(hipMemcpyAsync(dW, W, lw * sizeof(double), hipMemcpyHostToDevice, g.st), WHO);
+  HIPCHK(hipMemcpyAsync(dH, H, lh * sizeof(double), hipMemcpyHostToDevice, g.st), WHO);
   auto grid = [](long cnt) { return dim3((unsigned)((cnt + GB - 1) / GB)); };
-  const double* dA = g.dA;
+  const double* dA = g.dA.as<double>();
   int hstate[4] = {0, 0, 0, 0};
   int it = 0;
   for (; it < maxiter;) {
@@ -236,7 +164,7 @@ int mu_generic_call(const double* A, int m, int n, int k, int maxiter, int stop_
                          1L, (long)k);
       hipLaunchKernelGGL(k_gen_prod, grid((long)k * n), dim3(GB), 0, g.st, k, n, k, wtw, (long)k, 1L, dH, 1L, (long)k, denh,
                          1L, (long)k);
-      hipLaunchKernelGGL(k_gen_rule, grid((long)lh), dim3(GB), 0, g.st, (long)lh, dH, numh, denh, g.state);
+      hipLaunchKernelGGL(k_gen_rule, grid((long)lh), dim3(GB), 0, g.st, (long)lh, dH, numh, denh, state);
       // W side (nmf_mu.c:198-216) with the new h: numerw = A h^T, hht = h h^T, wden = W0 hht, W rule
       hipLaunchKernelGGL(k_gen_prod, grid((long)m * k), dim3(GB), 0, g.st, m, k, n, dA, (long)m, 1L, dH, (long)k, 1L, numw,
                          1L, (long)m);
@@ -244,20 +172,40 @@ int mu_generic_call(const double* A, int m, int n, int k, int maxiter, int stop_
                          1L, (long)k);
       hipLaunchKernelGGL(k_gen_prod, grid((long)m * k), dim3(GB), 0, g.st, m, k, k, dW, (long)m, 1L, hht, 1L, (long)k, denw,
                          1L, (long)m);
-      hipLaunchKernelGGL(k_gen_rule, grid((long)lw), dim3(GB), 0, g.st, (long)lw, dW, numw, denw, g.state);
-      hipLaunchKernelGGL(k_gen_check, dim3(1), dim3(GB), 0, g.st, iter, maxiter, stop_rule, k, n, dH, cls, g.state);
+      hipLaunchKernelGGL(k_gen_rule, grid((long)lw), dim3(GB), 0, g.st, (long)lw, dW, numw, denw, state);
+      hipLaunchKernelGGL(k_gen_check, dim3(1), dim3(GB), 0, g.st, iter, maxiter, stop_rule, k, n, dH, cls, state);
     }
-    GCHECK(hipGetLastError());
-    GCHECK(hipMemcpyAsync(hstate, g.state, sizeof(int) * 4, hipMemcpyDeviceToHost, g.st));
-    GCHECK(hipStreamSynchronize(g.st));
+    HIPCHK(hipGetLastError(), WHO);
+    HIPCHK(hipMemcpyAsync(hstate, state, sizeof(int) * 4, hipMemcpyDeviceToHost, g.st), WHO);
+    HIPCHK(hipStreamSynchronize(g.st), WHO);
     if (hstate[0]) break;
   }
-  GCHECK(hipMemcpyAsync(W, dW, lw * sizeof(double), hipMemcpyDeviceToHost, g.st));
-  GCHECK(hipMemcpyAsync(H, dH, lh * sizeof(double), hipMemcpyDeviceToHost, g.st));
-  GCHECK(hipMemcpyAsync(hstate, g.state, sizeof(int) * 4, hipMemcpyDeviceToHost, g.st));
-  GCHECK(hipStreamSynchronize(g.st));
+  HIPCHK(hipMemcpyAsync(W, dW, lw * sizeof(double), hipMemcpyDeviceToHost, g.st), WHO);
+  HIPCHK(hipMemcpyAsync(H, dH, lh * sizeof(double), hipMemcpyDeviceToHost, g.st), WHO);
+  HIPCHK(hipMemcpyAsync(hstate, state, sizeof(int) * 4, hipMemcpyDeviceToHost, g.st), WHO);
+  HIPCHK(hipStreamSynchronize(g.st), WHO);
   if (iters) *iters = maxiter == 0 ? 0 : hstate[1];
   if (early) *early = hstate[2] == 1;
   return 0;
 }
+
 }  // namespace
+
+// nmfc_nmf_mu_release (compat.hip): the device copy of A, the work buffers, the stream and the host copy of A
+extern "C" void nmfc_generic_release() {
+  std::lock_guard<std::mutex> lock(g.lock);
+  g.drop();
+}
+
+// The device copy of A, the work buffers and the stream are kept across calls under the rules of
+// nmfc_host::cached_call.
+extern "C" int nmfc_mu_generic(const double* A, int m, int n, int k, int maxiter, int stop_rule, double* W, double* H,
+                               int* iters, int* early) {
+  if (!A || !W || !H || m < 1 || n < 1 || k < 1 || k > m || k > n || maxiter < 0 ||
+      !nmfc_mu_stop_rule_ok(stop_rule)) {
+    nmfc_set_error("nmfc_mu_generic: bad arguments");
+    return -1;
+  }
+  return nmfc_host::cached_call(g, WHO,
+                                [&] { return mu_generic_call(A, m, n, k, maxiter, stop_rule, W, H, iters, early); });
+}

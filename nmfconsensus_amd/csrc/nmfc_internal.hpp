@@ -10,8 +10,11 @@ namespace nmfc {
 struct SoloJob;   // nmfc_kernels.hpp
 }
 
+// Exported but in no public header: compat.hip is also built on its own and linked against the library (the host
+// sanitizer build of the drop-in's C), so what it calls in other translation units (nmfc_set_error and the two
+// release functions below) must resolve from outside.
 // engine.hip: the thread's error slot behind nmfc_last_error
-__attribute__((visibility("hidden"))) void nmfc_set_error(const char* msg);
+extern "C" void nmfc_set_error(const char* msg);
 
 // solo.hip: the batched one-workgroup-per-restart kernels on gct-sized shapes -- the kernel rank (2, 3, 4 or 8) that
 // takes rank k, and one launch of njobs jobs of kernel rank kp (0: every rank) on at most max_wgs workgroups
@@ -24,6 +27,8 @@ __attribute__((visibility("hidden"))) int nmfc_solo_batch_launch(const double* A
 
 // solo.hip: drops its per-process copy of A, work buffer and pinned staging (nmfc_nmf_mu_release, compat.hip)
 extern "C" void nmfc_solo_release();
+// generic.hip: drops its per-process copy of A, work buffers and stream (nmfc_nmf_mu_release, compat.hip)
+extern "C" void nmfc_generic_release();
 
 // the stop rules of the single-restart entries (nmfc_engine_mu1, nmfc_mu_solo, nmfc_mu_generic): not STOP_TOLX
 inline bool nmfc_mu_stop_rule_ok(int stop_rule) {

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/nmfc.h"
+#include "nmfc_host.hpp"
 #include "nmfc_internal.hpp"
 #include "nmfc_kernels.hpp"
 
@@ -903,53 +904,76 @@ hipError_t dispatch(int grid, int kp, const double* A, int m, int n, double* W, 
   }
 }
 
-struct SoloCache {   // device copy of the last A (compared byte for byte), work buffer, pinned staging
-  std::vector<double>* a = nullptr;   // no destructor: HIP may be torn down at exit
-  int m = 0, n = 0;
-  double* dA = nullptr;
-  double* dwork = nullptr;   // [state (2 ints, 16 B) | W m x k | H k x n]
-  double* pin = nullptr;     // pinned image of dwork
-  size_t cap = 0;            // doubles in dwork / pin
+struct SoloCache : nmfc_host::MuCacheBase {   // device copy of the last A, work buffer, pinned staging
+  nmfc_host::DevBuf dA;
+  nmfc_host::DevBuf dwork;   // [state (2 ints, 16 B) | W m x k | H k x n]
+  nmfc_host::PinBuf pin;     // pinned image of dwork
   hipStream_t st = nullptr;
-  int dev = -1;              // the HIP device every resource above lives on
+  void drop() {   // lock held: frees everything, so the next call starts from scratch
+    if (st) (void)hipStreamSynchronize(st);
+    dA.release();
+    dwork.release();
+    pin.release();
+    if (st) (void)hipStreamDestroy(st);
+    st = nullptr;
+    drop_key();
+  }
 };
-std::mutex g_lock;
-SoloCache g;
+SoloCache& g = *new SoloCache;   // never destroyed (nmfc_host.hpp, process exit)
 
-void cache_drop() {   // g_lock held: frees everything, so the next call starts from scratch
-  if (g.st) (void)hipStreamSynchronize(g.st);
-  if (g.dA) (void)hipFree(g.dA);
-  if (g.dwork) (void)hipFree(g.dwork);
-  if (g.pin) (void)hipHostFree(g.pin);
-  if (g.st) (void)hipStreamDestroy(g.st);
-  delete g.a;
-  g.a = nullptr;
-  g.dA = g.dwork = g.pin = nullptr;
-  g.st = nullptr;
-  g.cap = 0;
-  g.m = g.n = 0;
-  g.dev = -1;
-}
+constexpr char WHO[] = "nmfc_mu_solo";   // the entry point HIPCHK reports under
 
-int fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "nmfc_mu_solo: %s: %s", what, hipGetErrorString(e));
-  nmfc_set_error(buf);
-  return -1;
+int mu_solo_call(const double* A, int m, int n, int k, int maxiter, int stop_rule, const double* W0, const double* H0,
+                 double* W, double* H, int* iters, int* early) {
+  const int kp = solo_rank(n, k);   // the kernel's rank (k = 3 padded to 4 at n > 32)
+  const size_t la = (size_t)m * n, lw = (size_t)m * kp, lh = (size_t)kp * n;
+  if (!g.st) HIPCHK(hipStreamCreateWithFlags(&g.st, hipStreamNonBlocking), WHO);
+  if (!(g.dA.p && g.key.same(A, m, n))) {
+    g.key.set(A, m, n);
+    if (g.dA.ensure(la * sizeof(double))) return -1;
+    HIPCHK(hipMemcpyAsync(g.dA.p, A, la * sizeof(double), hipMemcpyHostToDevice, g.st), WHO);
+  }
+  const size_t need = 2 + lw + lh;
+  if (g.dwork.ensure(need * sizeof(double)) || g.pin.ensure(need * sizeof(double))) return -1;
+  double* pin = g.pin.as<double>();
+  double* dwork = g.dwork.as<double>();
+  if (kp == k) {
+    memcpy(pin + 2, W0, lw * sizeof(double));
+    memcpy(pin + 2 + lw, H0, lh * sizeof(double));
+  } else {   // W0 m x k -> m x kp with zero columns, H0 k x n -> kp x n with zero rows
+    memcpy(pin + 2, W0, (size_t)m * k * sizeof(double));
+    memset(pin + 2 + (size_t)m * k, 0, (size_t)m * (kp - k) * sizeof(double));
+    for (int c = 0; c < n; ++c)
+      for (int a = 0; a < kp; ++a) pin[2 + lw + (size_t)c * kp + a] = a < k ? H0[(size_t)c * k + a] : 0.0;
+  }
+  HIPCHK(hipMemcpyAsync(dwork + 2, pin + 2, (lw + lh) * sizeof(double), hipMemcpyHostToDevice, g.st), WHO);
+  int* dstate = reinterpret_cast<int*>(dwork);
+  double* dW = dwork + 2;
+  double* dH = dW + lw;
+  const SoloLayout lay{m, m, kp, 1, nullptr, nullptr, nullptr, 1};
+  HIPCHK(dispatch(1, kp, g.dA.as<double>(), m, n, dW, dH, maxiter, stop_rule, dstate, k, lay, g.st), WHO);
+  HIPCHK(hipMemcpyAsync(pin, dwork, need * sizeof(double), hipMemcpyDeviceToHost, g.st), WHO);
+  HIPCHK(hipStreamSynchronize(g.st), WHO);
+  int hstate[2];
+  memcpy(hstate, pin, sizeof hstate);
+  memcpy(W, pin + 2, (size_t)m * k * sizeof(double));   // the first k columns of the m x kp W
+  if (kp == k) {
+    memcpy(H, pin + 2 + lw, lh * sizeof(double));
+  } else {
+    for (int c = 0; c < n; ++c)
+      for (int a = 0; a < k; ++a) H[(size_t)c * k + a] = pin[2 + lw + (size_t)c * kp + a];
+  }
+  if (iters) *iters = maxiter == 0 ? 0 : hstate[0];
+  if (early) *early = hstate[1] == 1;
+  return 0;
 }
 
 }  // namespace
 
-#define SCHECK(x)                                \
-  do {                                           \
-    hipError_t e_ = (x);                         \
-    if (e_ != hipSuccess) return fail(#x, e_);   \
-  } while (0)
-
 // nmfc_nmf_mu_release (compat.hip): the device copy of A, the work buffer and the pinned staging
 extern "C" void nmfc_solo_release() {
-  std::lock_guard<std::mutex> lock(g_lock);
-  cache_drop();
+  std::lock_guard<std::mutex> lock(g.lock);
+  g.drop();
 }
 
 // every shape with 2 <= k <= 8, k <= m <= 1024, k <= n <= 40 (ranks 5..8 on k_solo8_mu, A's last one to three
@@ -961,14 +985,8 @@ extern "C" int nmfc_mu_solo_fits(int m, int n, int k) {
   return m >= k && n >= k && k >= 2 && k <= 8 && m <= SOLO_MMAX && n <= SOLO_NMAX;
 }
 
-namespace {
-int mu_solo_call(const double* A, int m, int n, int k, int maxiter, int stop_rule, const double* W0, const double* H0,
-                 double* W, double* H, int* iters, int* early);
-}
-
 // The device copy of A, the work buffer, the pinned staging and the stream are kept across calls (nmf.r calls
-// nmf_mu once per restart on one matrix) on the device of the call that made them: a call on another device, a
-// failed call (nothing cached may hold a half-done upload) and NMFC_NMF_MU_CACHE=0 (after the call) free them.
+// nmf_mu once per restart on one matrix) under the rules of nmfc_host::cached_call.
 extern "C" int nmfc_mu_solo(const double* A, int m, int n, int k, int maxiter, int stop_rule, const double* W0,
                             const double* H0, double* W, double* H, int* iters, int* early) {
   if (!A || !W0 || !H0 || !W || !H || !nmfc_mu_solo_fits(m, n, k) || maxiter < 0 ||
@@ -976,76 +994,9 @@ extern "C" int nmfc_mu_solo(const double* A, int m, int n, int k, int maxiter, i
     nmfc_set_error("nmfc_mu_solo: bad arguments (needs 2 <= k <= 8, k <= m <= 1024, k <= n <= 40)");
     return -1;
   }
-  std::lock_guard<std::mutex> lock(g_lock);
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return fail("hipGetDevice", hipErrorInvalidDevice);
-  if (g.dev >= 0 && g.dev != dev) cache_drop();
-  const int rc = mu_solo_call(A, m, n, k, maxiter, stop_rule, W0, H0, W, H, iters, early);
-  const char* env = getenv("NMFC_NMF_MU_CACHE");
-  if (rc != 0 || (env && atoi(env) == 0))
-    cache_drop();
-  else
-    g.dev = dev;
-  return rc;
+  return nmfc_host::cached_call(
+      g, WHO, [&] { return mu_solo_call(A, m, n, k, maxiter, stop_rule, W0, H0, W, H, iters, early); });
 }
-
-namespace {
-int mu_solo_call(const double* A, int m, int n, int k, int maxiter, int stop_rule, const double* W0, const double* H0,
-                 double* W, double* H, int* iters, int* early) {
-  const int kp = solo_rank(n, k);   // the kernel's rank (k = 3 padded to 4 at n > 32)
-  const size_t la = (size_t)m * n, lw = (size_t)m * kp, lh = (size_t)kp * n;
-  if (!g.st) SCHECK(hipStreamCreateWithFlags(&g.st, hipStreamNonBlocking));
-  if (!(g.dA && g.m == m && g.n == n && memcmp(g.a->data(), A, la * sizeof(double)) == 0)) {
-    if (g.dA) (void)hipFree(g.dA);
-    g.dA = nullptr;
-    delete g.a;
-    g.a = new std::vector<double>(A, A + la);
-    g.m = m;
-    g.n = n;
-    SCHECK(hipMalloc(&g.dA, la * sizeof(double)));
-    SCHECK(hipMemcpyAsync(g.dA, A, la * sizeof(double), hipMemcpyHostToDevice, g.st));
-  }
-  const size_t need = 2 + lw + lh;
-  if (g.cap < need) {
-    if (g.dwork) (void)hipFree(g.dwork);
-    if (g.pin) (void)hipHostFree(g.pin);
-    g.dwork = g.pin = nullptr;
-    g.cap = 0;
-    SCHECK(hipMalloc(&g.dwork, need * sizeof(double)));
-    SCHECK(hipHostMalloc(&g.pin, need * sizeof(double), hipHostMallocDefault));
-    g.cap = need;
-  }
-  if (kp == k) {
-    memcpy(g.pin + 2, W0, lw * sizeof(double));
-    memcpy(g.pin + 2 + lw, H0, lh * sizeof(double));
-  } else {   // W0 m x k -> m x kp with zero columns, H0 k x n -> kp x n with zero rows
-    memcpy(g.pin + 2, W0, (size_t)m * k * sizeof(double));
-    memset(g.pin + 2 + (size_t)m * k, 0, (size_t)m * (kp - k) * sizeof(double));
-    for (int c = 0; c < n; ++c)
-      for (int a = 0; a < kp; ++a) g.pin[2 + lw + (size_t)c * kp + a] = a < k ? H0[(size_t)c * k + a] : 0.0;
-  }
-  SCHECK(hipMemcpyAsync(g.dwork + 2, g.pin + 2, (lw + lh) * sizeof(double), hipMemcpyHostToDevice, g.st));
-  int* dstate = reinterpret_cast<int*>(g.dwork);
-  double* dW = g.dwork + 2;
-  double* dH = dW + lw;
-  const SoloLayout lay{m, m, kp, 1, nullptr, nullptr, nullptr, 1};
-  SCHECK(dispatch(1, kp, g.dA, m, n, dW, dH, maxiter, stop_rule, dstate, k, lay, g.st));
-  SCHECK(hipMemcpyAsync(g.pin, g.dwork, need * sizeof(double), hipMemcpyDeviceToHost, g.st));
-  SCHECK(hipStreamSynchronize(g.st));
-  int hstate[2];
-  memcpy(hstate, g.pin, sizeof hstate);
-  memcpy(W, g.pin + 2, (size_t)m * k * sizeof(double));   // the first k columns of the m x kp W
-  if (kp == k) {
-    memcpy(H, g.pin + 2 + lw, lh * sizeof(double));
-  } else {
-    for (int c = 0; c < n; ++c)
-      for (int a = 0; a < k; ++a) H[(size_t)c * k + a] = g.pin[2 + lw + (size_t)c * kp + a];
-  }
-  if (iters) *iters = maxiter == 0 ? 0 : hstate[0];
-  if (early) *early = hstate[1] == 1;
-  return 0;
-}
-}  // namespace
 
 // Batched form (nmfc_engine_run, small shapes), reading the engine's column-major Acm and the stacked W/H at each
 // job's col0, stop state into stop_iter / stop_reason[rid]:
@@ -1068,10 +1019,10 @@ __attribute__((visibility("hidden"))) int nmfc_solo_batch_launch(const double* A
   }
   const SoloLayout lay{a_ld, w_ld, 1, h_ld, djobs, stop_iter, stop_reason, njobs};
   if (kp == 0) {
-    SCHECK(dispatch_batch(Acm, m, n, W, H, maxiter, stop_rule, lay, st));
+    HIPCHK(dispatch_batch(Acm, m, n, W, H, maxiter, stop_rule, lay, st), WHO);
   } else {
     const int grid = std::max(1, std::min(njobs, max_wgs > 0 ? max_wgs : njobs));
-    SCHECK(dispatch(grid, kp, Acm, m, n, W, H, maxiter, stop_rule, nullptr, kp, lay, st));
+    HIPCHK(dispatch(grid, kp, Acm, m, n, W, H, maxiter, stop_rule, nullptr, kp, lay, st), WHO);
   }
   return 0;
 }

@@ -1,6 +1,6 @@
 // lane_pool_driver.cpp -- the Brunet sweep's lane scheduler (csrc/lane_pool.hpp) with a stub job, for
 // tests/test_host_sanitizers.py under ThreadSanitizer (and ASan + UBSan).  The stub does what br_run_k does to shared
-// state: per-lane scratch that grows (Buf::ensure), a thread-local error string set on failure, per-lane iteration
+// state: per-lane scratch that grows (DevBuf::ensure), a thread-local error string set on failure, per-lane iteration
 // tallies, and writes into the caller's output arrays at its own job index only.  Checks: every job runs exactly
 // once, outputs equal a serial run, a failing job stops the others from starting new jobs and its message is the one
 // returned, and lane counts 1..8 all agree.

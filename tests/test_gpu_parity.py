@@ -174,7 +174,7 @@ def test_nmf_mu_abi(golden):
 def test_nmf_mu_cache_follows_content(golden, monkeypatch):
     """The engine nmf_mu keeps across calls is reused only for the same A: A then A' (same shape, one entry
     changed) then A again must each give what an uncached call gives (NMFC_NMF_MU_CACHE=0).  NMFC_SOLO=0 keeps
-    k = 3 off the solo kernel, so the engine path and its cache (compat.hip mu_cache_drop) are the ones tested."""
+    k = 3 off the solo kernel, so the engine path and its cache (compat.hip MuCache) are the ones tested."""
     from nmfconsensus_amd import _lib, libnmf
     _lib.lib().nmfc_nmf_mu_release()
     monkeypatch.setenv("NMFC_SOLO", "0")
@@ -210,6 +210,26 @@ def test_nmf_mu_solo_cache_follows_content(golden):
         _lib.lib().nmfc_nmf_mu_release()
         fresh.append(libnmf.nmf_mu(X, W0, H0, 40))
     for c, f in zip(cached, fresh + fresh[:1]):
+        assert np.array_equal(c["w0"], f["w0"]) and np.array_equal(c["h0"], f["h0"])
+    assert not np.array_equal(cached[0]["h0"], cached[1]["h0"])
+
+
+def test_nmf_mu_generic_cache_follows_content(golden):
+    """The generic path (k = 20 on the gct) keeps its device copy of A across calls only for the same A: A, A' (one
+    entry changed), A again give what a call after nmfc_nmf_mu_release (nothing cached) gives."""
+    from nmfconsensus_amd import _lib, libnmf
+    A = golden["A_gct"]
+    A2 = A.copy(order="F")
+    A2[517, 23] += 0.25
+    rng = np.random.default_rng(2040)
+    W0, H0 = rng.uniform(0.1, 1.0, (A.shape[0], 20)), rng.uniform(0.1, 1.0, (20, A.shape[1]))
+    cached = [libnmf.nmf_mu(X, W0, H0, 40) for X in (A, A2, A)]
+    fresh = []
+    for X in (A, A2):
+        _lib.lib().nmfc_nmf_mu_release()
+        fresh.append(libnmf.nmf_mu(X, W0, H0, 40))
+    for c, f in zip(cached, fresh + fresh[:1]):
+        assert c["ret"] == 0 and f["ret"] == 0
         assert np.array_equal(c["w0"], f["w0"]) and np.array_equal(c["h0"], f["h0"])
     assert not np.array_equal(cached[0]["h0"], cached[1]["h0"])
 

@@ -8,6 +8,8 @@ CPU only, no GPU: the GPU pool runs no sanitizer builds, so the host-side C/C++ 
   anchor) built with ASan + UBSan and loaded in a child interpreter that then re-runs golden cases through it.
 * the drop-in's host C (csrc/compat.hip) built with -Xarch_host -fsanitize=address,undefined and driven by
   tests/sanitize/compat_driver.c (argument / matrix checks, generateMatrix against the golden init).
+* the library's shared host runtime (csrc/nmfc_host.hpp) built the same way with
+  tests/sanitize/host_runtime_driver.cpp: the parts that need no device (matrix key, buffer moves, errorf).
 """
 import os
 import shutil
@@ -164,3 +166,26 @@ def test_brunet_lane_pool_sanitized(san):
         r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=ENV)
         assert r.returncode == 0 and "lane pool driver ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
         assert "WARNING: ThreadSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
+HOST_RUNTIME_DRIVER = os.path.join(ROOT, "tests", "sanitize", "host_runtime_driver.cpp")
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_host_runtime_asan_ubsan():
+    """csrc/nmfc_host.hpp with tests/sanitize/host_runtime_driver.cpp (a stand-alone program, its host side compiled
+    with -Xarch_host -fsanitize=address,undefined): the drop-in caches' matrix key (same content matches; one changed
+    entry or another shape does not; empty after a drop), moves of empty and of owning DevBuf / PinBuf objects (the
+    moved-from object holds p == nullptr and bytes == 0, nothing is released twice) and errorf's truncation of a
+    2000-character argument at its buffer size.  The driver makes no HIP allocation call: no GPU is needed."""
+    with tempfile.TemporaryDirectory() as td:
+        exe = os.path.join(td, "host_runtime_driver")
+        hostsan = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
+                   "-Xarch_host", "-fno-sanitize-recover=all"]
+        r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-x", "hip", "-O1", "-g", "-fno-omit-frame-pointer",
+                            "-std=c++17", *hostsan, "-fno-gpu-sanitize", HOST_RUNTIME_DRIVER, "-o", exe],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=ENV)
+        assert r.returncode == 0 and "host runtime driver ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+        assert "runtime error" not in r.stderr, r.stderr[-4000:]
