@@ -305,7 +305,10 @@ double nmfc_engine_kernel_bytes(nmfc_engine* e, int kernel_id, double* algo_byte
  * packing would not fit the buffers; polls: reads of the stop count enqueued; iterations_enqueued: MU iterations
  * launched; panels_first / panels_min: 64-column panels (padded) of the first / the smallest packing;
  * wta_narrow, wta_sk, wta_big, wta_mid, wta_small, wta_tiny: iterations launched per W^T A form (narrow tail kernel,
- * stream-K, 4-panel, 2-panel, 1 x 64 and 1 x 32 tiles); ahtw_narrow, ahtw_128, ahtw_64: the same per A h^T form. */
+ * stream-K, 4-panel, 2-panel, 1 x 64 and 1 x 32 tiles); ahtw_narrow, ahtw_128, ahtw_64: the same per A h^T form;
+ * wta_sk_nowait: how many of the wta_sk launches ran the stream-K tile's NOWAIT instantiation (the test hook
+ * NMFC_WTA_SK_NOWAIT=1) -- a sub-count of wta_sk, not a form of its own; sk_wraps: times the stream-K launch
+ * counter (the hand-off flag value) wrapped past 2^32 - 1 in the run, each time zeroing the flags and restarting at 1. */
 const char* nmfc_engine_run_info(nmfc_engine* e);
 
 #ifdef __cplusplus

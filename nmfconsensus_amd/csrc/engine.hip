@@ -253,8 +253,13 @@ struct nmfc_engine {
   bool wta_sk_mid = true;           // env NMFC_WTA_SK_MID=0: the same for the 2-panel tile
   bool wta_lastsum = false;         // env NMFC_WTA_LASTSUM=1: k_wta2_sk sums each tile's chunk partials (probe arm)
   int sk_dp_xcd = 0;                // env NMFC_SK_DP_XCD=1: k_wta2_sk's whole rounds in XCD-contiguous blocks (probe)
+  bool wta_sk_nowait = false;       // env NMFC_WTA_SK_NOWAIT=1 (test hook): k_wta2_sk's NOWAIT instantiations -- no
+                                    // continuation polls, every one recomputes its item from stage 0 (the path a
+                                    // poll time-out takes; the same bits, slower).  Ignored by the LASTSUM probe arm
   DevBuf skfix, skflag, sktcnt;     // k_wta2_sk: per-range hand-off slots and flags (zeroed once), per-tile tickets
-  unsigned sk_epoch = 0;            // k_wta2_sk launches so far (the flag value of the current launch)
+  unsigned sk_epoch = 0;            // the flag value of the last k_wta2_sk launch: 1, 2, ... and never 0, the value of
+                                    // a slot nobody has published (env NMFC_WTA_SK_EPOCH0=<unsigned>, a test hook,
+                                    // sets the start so that a short run crosses the 32-bit wrap)
   bool gram_model = true;           // env NMFC_GRAM_MODEL=0: the tile cost model without the Gram workgroups
   bool solo_ok = true;              // env NMFC_SOLO=0: no solo kernel (every small-shape restart in k_small_mu blocks)
   hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};   // the solo launches (one per kernel rank: 2, 3, 4, 8)
@@ -284,6 +289,8 @@ struct nmfc_engine {
   struct RunInfo {
     int small = 0, repacks_skipped = 0, polls = 0, iterations_enqueued = 0, panels_first = 0, panels_min = 0;
     long long wta_narrow = 0, wta_sk = 0, wta_big = 0, wta_mid = 0, wta_small = 0, wta_tiny = 0;   // iterations per W^T A form
+    long long wta_sk_nowait = 0;   // of wta_sk: launches of the NOWAIT instantiations (NMFC_WTA_SK_NOWAIT)
+    long long sk_wraps = 0;        // times the stream-K epoch wrapped in this run (flags zeroed, epoch back to 1)
     long long ahtw_narrow = 0, ahtw_128 = 0, ahtw_64 = 0;                                         // ... per A h^T form
   } info;
   std::string info_str;
@@ -978,6 +985,8 @@ void launch_wta_narrow(const Sweep& s, int nblk) {
                      s.sw_total);
 }
 
+int launch_wta_sk_nowait(nmfc_engine* e, bool big, const SkArgs& a);   // at the end of this file
+
 // stream-K form of the big (4-panel) or 2-panel tile over ng groups: ncu persistent workgroups, whole rounds of items
 // then the rest split evenly (bit-identical to the one-item-per-workgroup tile: the same MFMA chains, handed over at a
 // stage boundary).  *gsplit = 1 after a LASTSUM launch.
@@ -991,6 +1000,16 @@ int launch_wta_sk(Sweep& s, bool big, int ng, int* gsplit) {
   ++e->info.wta_sk;
   const long tiles = (long)ng * s.ntj;
   const bool lastsum = e->wta_lastsum && big;
+  const bool nowait = e->wta_sk_nowait && !lastsum;
+  e->info.wta_sk_nowait += nowait;
+  // the epoch is the flag value and 0 is the value of a slot never published: on the 32-bit wrap every slot goes back
+  // to 0 (in stream order, after the launches that read them) and the count restarts at 1, so no stale slot holds a
+  // live epoch
+  if (++e->sk_epoch == 0) {
+    HIPCHK(hipMemsetAsync(e->skflag.p, 0, sizeof(unsigned) * e->ncu, st));
+    e->sk_epoch = 1;
+    ++e->info.sk_wraps;
+  }
   if (lastsum && e->sktcnt.bytes < sizeof(unsigned) * tiles) {
     if (e->sktcnt.ensure(sizeof(unsigned) * tiles)) return -1;   // fresh tickets: zero
     HIPCHK(hipMemsetAsync(e->sktcnt.p, 0, sizeof(unsigned) * tiles, st));
@@ -998,9 +1017,11 @@ int launch_wta_sk(Sweep& s, bool big, int ng, int* gsplit) {
   const SkArgs a{e->W[s.cur].as<double>(), e->Ablk.as<double>(), e->m_pad, ng, s.ntj, e->kchunk,
                  e->prb.as<int>(), e->pre.as<int>(), e->rinfo.as<RestartInfo>(), e->colinfo.as<ColInfo>(),
                  e->stop_iter.as<int>(), e->Gpart.as<double>(), s.g_ld, s.g_split, e->SWpart.as<double>(), s.sw_total,
-                 e->skfix.as<double>(), e->skflag.as<unsigned>(), ++e->sk_epoch, e->nsplit,
+                 e->skfix.as<double>(), e->skflag.as<unsigned>(), e->sk_epoch, e->nsplit,
                  e->sktcnt.as<unsigned>(), e->sk_dp_xcd};
-  if (!big) {
+  if (nowait) {   // the test hook's two instantiations, named after the product's (which keep their place in the code object)
+    return launch_wta_sk_nowait(e, big, a);
+  } else if (!big) {
     hipLaunchKernelGGL((k_wta2_sk<WTA_MID_NBUF, false, false, 2>), dim3(e->ncu), dim3(SK_THREADS / 2), 0, st, a);
   } else if (lastsum) {
     hipLaunchKernelGGL((k_wta2_sk<GT_NBUF, false, true>), dim3(e->ncu), dim3(SK_THREADS), 0, st, a);
@@ -1536,6 +1557,8 @@ nmfc_engine* nmfc_engine_create(int device, const double* A, int m, int n, int a
   if (const char* s = getenv("NMFC_NARROW_LC")) e->narrow_lc = atoi(s) != 0;
   if (const char* s = getenv("NMFC_WTA_SK")) e->wta_sk = atoi(s) != 0;
   if (const char* s = getenv("NMFC_WTA_SK_MID")) e->wta_sk_mid = atoi(s) != 0;
+  if (const char* s = getenv("NMFC_WTA_SK_NOWAIT")) e->wta_sk_nowait = atoi(s) != 0;
+  if (const char* s = getenv("NMFC_WTA_SK_EPOCH0")) e->sk_epoch = (unsigned)strtoul(s, nullptr, 10);
   if (const char* s = getenv("NMFC_WTA_LASTSUM")) e->wta_lastsum = atoi(s) != 0;
   if (const char* s = getenv("NMFC_SK_DP_XCD")) e->sk_dp_xcd = atoi(s) != 0;
   if (const char* s = getenv("NMFC_GRAM_MODEL")) e->gram_model = atoi(s) != 0;
@@ -1730,13 +1753,14 @@ double nmfc_engine_kernel_bytes(nmfc_engine* e, int kid, double* algo_bytes_out)
 const char* nmfc_engine_run_info(nmfc_engine* e) {
   if (!e) return "";
   const nmfc_engine::RunInfo& i = e->info;
-  char buf[640];
+  char buf[704];
   snprintf(buf, sizeof buf,
            "small=%d;repacks=%d;repacks_skipped=%d;polls=%d;iterations_enqueued=%d;panels_first=%d;panels_min=%d;"
            "wta_narrow=%lld;wta_sk=%lld;wta_big=%lld;wta_mid=%lld;wta_small=%lld;wta_tiny=%lld;"
-           "ahtw_narrow=%lld;ahtw_128=%lld;ahtw_64=%lld",
+           "ahtw_narrow=%lld;ahtw_128=%lld;ahtw_64=%lld;wta_sk_nowait=%lld;sk_wraps=%lld",
            i.small, e->repacks, i.repacks_skipped, i.polls, i.iterations_enqueued, i.panels_first, i.panels_min,
-           i.wta_narrow, i.wta_sk, i.wta_big, i.wta_mid, i.wta_small, i.wta_tiny, i.ahtw_narrow, i.ahtw_128, i.ahtw_64);
+           i.wta_narrow, i.wta_sk, i.wta_big, i.wta_mid, i.wta_small, i.wta_tiny, i.ahtw_narrow, i.ahtw_128, i.ahtw_64,
+           i.wta_sk_nowait, i.sk_wraps);
   e->info_str = buf;
   return e->info_str.c_str();
 }
@@ -1932,3 +1956,19 @@ int nmfc_sweep(const double* A, int m, int n, const int* ks, int nk, int R, cons
 }
 
 }  // extern "C"
+
+namespace {
+
+// NMFC_WTA_SK_NOWAIT=1 (test hook): launch_wta_sk's launch with k_wta2_sk's NOWAIT instantiations, in which no
+// continuation polls and every one recomputes its item from stage 0 -- the path a poll time-out takes on a shared GPU.
+// Defined last: the compiler emits kernels in the order this file names them, so the two test instantiations follow every
+// product kernel in the code object and those keep their layout.
+int launch_wta_sk_nowait(nmfc_engine* e, bool big, const SkArgs& a) {
+  if (big)
+    hipLaunchKernelGGL((k_wta2_sk<GT_NBUF, true>), dim3(e->ncu), dim3(SK_THREADS), 0, e->st, a);
+  else
+    hipLaunchKernelGGL((k_wta2_sk<WTA_MID_NBUF, true, false, 2>), dim3(e->ncu), dim3(SK_THREADS / 2), 0, e->st, a);
+  return 0;
+}
+
+}  // namespace

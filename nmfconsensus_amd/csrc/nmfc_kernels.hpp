@@ -1065,7 +1065,7 @@ __device__ __forceinline__ void wta_sk_piece(int r, int item_in, int s0_in, int 
   }
 }
 
-// NOWAIT (tools/kvar.hip only): every continuation takes the recompute path (tests its bits)
+// NOWAIT (tools/kvar.hip, and the engine under NMFC_WTA_SK_NOWAIT=1): every continuation takes the recompute path (tests its bits)
 template <int NBUF = GT_NBUF, bool NOWAIT = false, bool LSUM = false, int NPT = 4>
 static __global__ __launch_bounds__(64 * NPT * 4, 1) void k_wta2_sk(SkArgs args) {
   using T = GTile<64 * NPT, 128, NPT, 4, NBUF, true, true, true, true>;

@@ -348,6 +348,12 @@ def test_wta_stream_k_bit_identical(oracle, m, R, lastsum, tile):
             os.environ["NMFC_WTA_LASTSUM"] = lastsum if sk == "1" else "0"   # the split-K combine probe arm (round 6)
             with Engine(A) as eng:
                 runs[sk] = eng.run(ks, R, maxiter=T, seed=9, stop_rule=0, want_factors=True, want_counts=False)
+                info = eng.last_run_info()
+            # the arms ran what they name: every launch the stream-K tile, or none (else k_wta2 is compared with itself)
+            assert info["iterations_enqueued"] == T and info["wta_sk_nowait"] == 0, (sk, info)
+            assert info["wta_sk"] == (T if sk == "1" else 0), (sk, info)
+            assert info["wta_" + tile] == (0 if sk == "1" else T), (sk, info)
+            assert all(info[k] == 0 for k in ("wta_narrow", "wta_big", "wta_mid", "wta_small", "wta_tiny") if k != "wta_" + tile), (sk, info)
     finally:
         os.environ.pop("NMFC_WTA_TILE", None)
         os.environ.pop("NMFC_WTA_SK", None)

@@ -48,7 +48,10 @@ def _usage(src):
 # engine kernels allowed a pinned spill count: k_wta2_sk (the stream-K W^T A tiles) reloads a few VGPRs once per piece,
 # outside its K loops (test_wta_sk_k_loops_spill_free checks the loops themselves): 3 in the engine's 4-panel form (ROCm
 # 7.2 hipcc, round 6 final), 12 in the LSUM probe arm (its last-arriver sum after the loop), 0 in the 2-panel form
-ENGINE_SPILLS = {"k_wta2_skILi3ELb0ELb0ELi4E": 3, "k_wta2_skILi3ELb0ELb1ELi4E": 12}
+# The NOWAIT instantiations (the test hook NMFC_WTA_SK_NOWAIT: no poll loop, otherwise the same code) spill what their
+# product forms do: 3 in the 4-panel form, 0 in the 2-panel form; test_wta_sk_k_loops_spill_free covers their K loops too
+ENGINE_SPILLS = {"k_wta2_skILi3ELb0ELb0ELi4E": 3, "k_wta2_skILi3ELb0ELb1ELi4E": 12,
+                 "k_wta2_skILi3ELb1ELb0ELi4E": 3, "k_wta2_skILi3ELb1ELb0ELi2E": 0}
 
 
 def _short(mangled):
@@ -184,7 +187,7 @@ def test_wta_sk_k_loops_spill_free():
     # the engine's forms: the 4-panel tile and the 2-panel tile (not the LSUM probe arm, k_wta2_sk<3, false, true>: it
     # reloads spilled values inside its K loops since the whole-round order, one reason it stays a probe)
     starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\S*k_wta2_sk\S*:", l) and "k_wta2_skILi3ELb0ELb1E" not in l]
-    assert len(starts) >= 2, [lines[i] for i in starts]
+    assert len(starts) >= 4, [lines[i] for i in starts]   # ... each with its NOWAIT instantiation (the test hook)
     for start in starts:
         end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
         depth, inner_mfma, inner_scratch, blocks = 0, 0, 0, 0
