@@ -67,6 +67,34 @@ typedef struct options_t {
 double nmf_mu(double* a, double* w0, double* h0, int* pm, int* pn, int* pk, int* maxiter,
               const double* pTolX, const double* pTolFun);
 
+/*
+ * nmf_neals -- replaces libnmf/nmf_neals.c:86-87: normal-equation ALS.  Per iteration H <- max(0, (W0^T W0)^-1 W0^T A)
+ * and W <- max(0, (H H^T)^-1 H A^T)^T, both k x k systems by LU with partial pivoting (dgesv, :204 and :306), then
+ * delta = max(calculateMaxchange(W, W0), calculateMaxchange(H, H0)); on every iteration > 1 the loop stops if
+ * delta < TolX, else if TolFun >= 1 (dnorm0 = dnorm is assigned at :438, before dnorm <= TolFun * dnorm0 is tested).
+ * *maxiter: in = cap, out = the stopping iteration (the cap when no test fired).  Returns calculateNorm of the final
+ * factors (the reference evaluates it every iteration; only the last value is observable, and it is evaluated once).
+ * Runs on the batched MFMA engine with a batch of one for 2 <= k <= 16 (the engine cache nmf_mu's engine route uses;
+ * nmfc_nmf_mu_release frees it).
+ *  - h0 is NOT an input: it never enters an update, only iteration 1's delta, which is not tested.  The results
+ *    depend on (a, k, w0, maxiter, TolX, TolFun) only.
+ *  - w0 / h0 hold the final factors on exit ALWAYS, and nothing of the caller's is freed.  The reference swaps its
+ *    local w0 / w pointers every iteration and frees `w` at the end (:432, :477): after an odd count that is the
+ *    caller's buffer, so the reference cannot return factors after an odd iteration count.
+ *  - The QR fallback (:206-291, :308-393) is not built.  When an LU meets an exactly zero pivot the job ends at that
+ *    iteration: one line naming the iteration goes to stderr, *maxiter is set to it and -1 is returned.  In the H solve
+ *    (status 1) w0 / h0 keep the factors of the last complete iteration; in the W solve (status 2) h0 holds that
+ *    iteration's H and w0 the previous iteration's W.
+ *  - k outside 2..16 prints "Error in nmf_neals: k=<k> unsupported (need 2 <= k <= 16)" to stderr before any device
+ *    work, leaves w0 / h0 untouched and returns -1.  A rank in 2..16 above min(m, n) is refused the same way, with
+ *    "Error in nmf_neals: k=<k> unsupported (need k <= min(m, n))" (the reference would hand dgesv a Gram matrix of
+ *    rank < k there).
+ *  - *maxiter < 1: the reference's loop does not run and its dnorm = 0 is returned (nmf_neals.c:134, :192); here too
+ *    0.0 comes back before any device work, with w0 / h0 and *maxiter untouched.
+ */
+double nmf_neals(double* a, double* w0, double* h0, int* pm, int* pn, int* pk, int* maxiter,
+                 const double* pTolX, const double* pTolFun);
+
 /* set_default_opts -- replaces libnmf/setdefaultopts.c:38-52 */
 void set_default_opts(options_t* opts);
 

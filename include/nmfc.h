@@ -136,6 +136,35 @@ int nmfc_engine_best(nmfc_engine* e, int32_t* best_job_out, double* best_dnorm_o
  * stopfreq are ignored then).  Returns 0, or -1 (nmfc_last_error) for a NULL engine, stopconv < 1 or stopfreq < 1. */
 int nmfc_engine_set_euclid(nmfc_engine* e, int enable, int stopconv, int stopfreq);
 
+/* libnmf's nmf_neals (nmf_neals.c:86-495), normal-equation ALS, on the MFMA engine.  enable != 0: later nmfc_engine_run
+ * calls run, per job and per iteration t = 1, 2, ... on column-major fp64 factors,
+ *     H <- max(0, X),  (W0^T W0) X = W0^T A        H[i] = X[i] > 0 ? X[i] : 0   (NaN, -0.0, negatives -> +0.0)
+ *     W <- max(0, Y)^T, (H H^T) Y = H A^T          if (W[i] < 0) W[i] = 0       (NaN and -0.0 pass)
+ * each system by LU with partial pivoting (dgesv: the first entry of largest magnitude of the column is the pivot,
+ * rows are interchanged, unit diagonal in L; the solve uses the factors, never an inverse), then
+ * delta = max(calculateMaxchange(W, W0), calculateMaxchange(H, H0)).
+ * opts->stop_rule: NMFC_STOP_FIXED runs exactly maxiter iterations; EVERY other value means nmf_neals' rule with
+ * opts->TolX / opts->TolFun, tested on every iteration > 1: stop if delta < TolX, else if TolFun >= 1 (see
+ * NMFC_STOP_TOLX).  stopped_early is 1 when that rule fired.
+ * H0 is not an input: it never enters an update, only iteration 1's delta, which is not tested; an H_init is accepted
+ * and ignored, and a job's results depend on (A, k, W0, maxiter, TolX, TolFun) only.  The final factors are returned
+ * after any iteration count (the reference can return them only after an even one: it frees the caller's buffer
+ * after an odd count, nmf_neals.c:432 / :477).
+ * The reference's QR fallback for an exactly zero pivot (info > 0) is not built: such a job ends at that iteration,
+ * iters = that iteration, stopped_early = 0, and nmfc_engine_neals_status reports 1 (zero pivot in the H solve: W and H
+ * are those of the last complete iteration) or 2 (in the W solve: H is that iteration's, W the previous one's).  The
+ * job still gets labels from the H it holds and is counted in the consensus.
+ * Seeds, job order (k fastest), job_begin / job_end, W_init, both init streams, the residual pass and nmfc_engine_best
+ * work as in every other run; the sweep always takes the MFMA kernels, so a job's bits depend on (A, k, seed or W_init,
+ * options) only.  enable == 0 restores the nmf_mu runs exactly.  Returns 0, or -1 (nmfc_last_error) for a NULL engine
+ * or when the Euclidean rule is enabled on that engine (nmfc_engine_set_euclid fails the same way while this rule is
+ * on: turn one off first). */
+int nmfc_engine_set_neals(nmfc_engine* e, int enable);
+
+/* Per shard job of the last run, indexed like nmfc_result.iters: 0, 1 or 2 (above).  status_out may be NULL.  Returns
+ * the job count, or -1 when the last run on this engine was not a NEALS run. */
+int nmfc_engine_neals_status(nmfc_engine* e, int32_t* status_out);
+
 /* Convenience: create, run, destroy. */
 /* One restart of nmf_mu (nmf_mu.c:84-315) on the small-shape team kernel (m rounded up to 128 <= 8192, n <= 64,
  * k <= 16), with one upload, one launch and one download: the per-call path of the nmf_mu drop-in (nmf.r:41-45).

@@ -53,12 +53,12 @@ class OptionsT(ctypes.Structure):
 
 EXPORTED = [
     # include/libnmf_compat.h
-    "nmf_mu", "set_default_opts", "checkArguments", "checkMatrices", "randnumber", "generateMatrix",
+    "nmf_mu", "nmf_neals", "set_default_opts", "checkArguments", "checkMatrices", "randnumber", "generateMatrix",
     "calculateNorm", "calculateMaxchange",
     # include/nmfc.h
     "nmfc_engine_create", "nmfc_engine_destroy", "nmfc_engine_device", "nmfc_current_device", "nmfc_engine_mu1", "nmfc_mu_generic", "nmfc_mu_solo_fits", "nmfc_mu_solo", "nmfc_brunet_device", "nmfc_default_opts", "nmfc_engine_run", "nmfc_sweep",
     "nmfc_consensus", "nmfc_cophenetic", "nmfc_cophenetic_batch", "nmfc_cutree", "nmfc_last_error", "nmfc_version", "nmfc_engine_kernel_time",
-    "nmfc_engine_set_timing", "nmfc_engine_set_residuals", "nmfc_engine_set_euclid", "nmfc_engine_residuals", "nmfc_engine_best", "nmfc_engine_kernel_flops", "nmfc_engine_kernel_bytes", "nmfc_engine_run_info",
+    "nmfc_engine_set_timing", "nmfc_engine_set_residuals", "nmfc_engine_set_euclid", "nmfc_engine_set_neals", "nmfc_engine_neals_status", "nmfc_engine_residuals", "nmfc_engine_best", "nmfc_engine_kernel_flops", "nmfc_engine_kernel_bytes", "nmfc_engine_run_info",
     "nmfc_calculate_norm_dev", "nmfc_calculate_maxchange_dev", "nmfc_nmf_mu_release",
     "nmfc_brunet_default_opts", "nmfc_brunet_create", "nmfc_brunet_destroy", "nmfc_brunet_run",
     "nmfc_brunet_set_timing", "nmfc_brunet_kernel_time", "nmfc_build_tuning", "nmfc_build_tuning_brunet",
@@ -146,6 +146,12 @@ def lib() -> ctypes.CDLL:
     L.nmfc_engine_set_residuals.restype = None
     L.nmfc_engine_set_euclid.argtypes = [ctypes.c_void_p, c_int, c_int, c_int]
     L.nmfc_engine_set_euclid.restype = c_int
+    L.nmf_neals.argtypes = [_dp, _dp, _dp, ip, ip, ip, ip, _dp, _dp]
+    L.nmf_neals.restype = ctypes.c_double
+    L.nmfc_engine_set_neals.argtypes = [ctypes.c_void_p, c_int]
+    L.nmfc_engine_set_neals.restype = c_int
+    L.nmfc_engine_neals_status.argtypes = [ctypes.c_void_p, _ip]
+    L.nmfc_engine_neals_status.restype = c_int
     L.nmfc_engine_residuals.argtypes = [ctypes.c_void_p, _dp]
     L.nmfc_engine_residuals.restype = c_int
     L.nmfc_engine_best.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp]

@@ -258,6 +258,80 @@ double nmf_mu(double* a, double* w0, double* h0, int* pm, int* pn, int* pk, int*
   return 0;
 }
 
+namespace {
+// one nmf_neals job on engine e (a batch of one under nmfc_engine_set_neals); the engine is handed back with the rule off
+int neals_engine_call(nmfc_engine* e, int k, int maxiter, double TolX, double TolFun, double* w0, double* h0,
+                      int32_t* iters, int32_t* status) {
+  if (nmfc_engine_set_neals(e, 1) != 0) return -1;
+  nmfc_sweep_opts o;
+  nmfc_default_opts(&o);
+  o.maxiter = maxiter;
+  o.stop_rule = NMFC_STOP_TOLX;
+  o.TolX = TolX;
+  o.TolFun = TolFun;
+  o.check_every = 64;
+  int32_t early = 0;
+  nmfc_result r = {};
+  r.iters = iters;
+  r.stopped_early = &early;
+  r.W = w0;
+  r.H = h0;
+  const int ks[1] = {k};
+  int rc = nmfc_engine_run(e, ks, 1, 1, &o, w0, h0, &r);
+  if (rc == 0 && nmfc_engine_neals_status(e, status) != 1) rc = -1;
+  (void)nmfc_engine_set_neals(e, 0);
+  return rc;
+}
+}  // namespace
+
+// nmf_neals.c:86-495 on the GPU engine (libnmf_compat.h)
+double nmf_neals(double* a, double* w0, double* h0, int* pm, int* pn, int* pk, int* maxiter, const double* pTolX,
+                 const double* pTolFun) {
+  const int m = *pm, n = *pn, k = *pk;
+  if (k < 2 || k > nmfc::KMAX) {   // checked before any device work
+    fprintf(stderr, "Error in nmf_neals: k=%d unsupported (need 2 <= k <= 16)\n", k);
+    return -1;
+  }
+  if (k > m || k > n) {
+    fprintf(stderr, "Error in nmf_neals: k=%d unsupported (need k <= min(m, n))\n", k);
+    return -1;
+  }
+  if (*maxiter < 1) return 0.0;   // the reference's loop does not run: dnorm = 0 (nmf_neals.c:134)
+  int32_t iters = 0, status = 0;
+  int rc = -1;
+  {
+    if (!nmfc_host::mu_cache_enabled()) {
+      nmfc_engine* e = nmfc_engine_create(-1, a, m, n, 0);
+      if (e) rc = neals_engine_call(e, k, *maxiter, *pTolX, *pTolFun, w0, h0, &iters, &status);
+      nmfc_engine_destroy(e);
+    } else {
+      rc = nmfc_host::cached_call(g_mu, "nmf_neals", [&] {
+        if (!(g_mu.e && g_mu.key.same(a, m, n))) {
+          g_mu.drop();
+          if (!(g_mu.e = nmfc_engine_create(-1, a, m, n, 0))) return -1;
+          g_mu.key.set(a, m, n);
+        }
+        return neals_engine_call(g_mu.e, k, *maxiter, *pTolX, *pTolFun, w0, h0, &iters, &status);
+      });
+    }
+    if (rc != 0) {
+      fprintf(stderr, "Error in nmf_neals: %s\n", nmfc_last_error());
+      return -1;
+    }
+    if (status != 0) {
+      fprintf(stderr,
+              "Error in nmf_neals: exactly zero pivot in the %s solve at iteration %d; the QR fallback is not implemented\n",
+              status == 1 ? "H" : "W", (int)iters);
+      *maxiter = iters;
+      return -1;
+    }
+    *maxiter = iters;   // the stopping iteration, or the cap
+  }
+  // the reference's return value: calculateNorm of the final factors (nmf_neals.c:411, :493)
+  std::vector<double> d((size_t)m * n);
+  return calculateNorm(a, w0, h0, d.data(), m, n, k);
+}
+
 // calculatenorm.c:44-78 on device operands: d = a - w h and ||d||_F / sqrt(m n), one fused GPU pass +
 // a host sum of the per-block partials in block order (deterministic).  ms_out: device time of the pass.
 int nmfc_calculate_norm_dev(const double* da, const double* dw, const double* dh, double* dd, int m, int n, int k,

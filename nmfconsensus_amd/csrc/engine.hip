@@ -297,6 +297,13 @@ struct nmfc_engine {
   // nmfc_engine_set_euclid: runs use the BROAD script's Euclidean NMF() rules, stop rule and seeding
   bool euclid = false;
   int euc_stopconv = 40, euc_stopfreq = 10;
+  // nmfc_engine_set_neals: runs use nmf_neals' normal-equation ALS update and its every-iteration TolX / TolFun rule.
+  // Craw: H A^T of the iteration (the A h^T kernels' output under this rule); lupiv: the row permutation of each
+  // restart's LU of H H^T (the LU itself is in SHP); wd / wo: per restart max |w0 - w| and max |w0| as bits.
+  // neals_status: per shard job of the last run 0, 1 (zero pivot in the H solve) or 2 (in the W solve)
+  bool neals = false, neals_valid = false;
+  DevBuf Craw, lupiv, neals_wd, neals_wo;
+  std::vector<int32_t> neals_status;
   // nmfc_engine_set_residuals: the residual pass of the results phase.  ssq: sum of d^2 per shard job of the last
   // run (device, and h_ssq on the host); respart: its per-(job, tile) partials.  last_*: what the getters need of that
   // run (the archive Wfin / Hfin lives until the next one): the shard, and each shard job's first archive row
@@ -550,7 +557,7 @@ struct Sweep {
   long cap_cols = 0;                // columns of the stacked buffers (from the first packing)
   int ntj = 0;                      // 128-sample tiles of W^T A
   long g_ld = 0, g_split = 0, cls_ld = 0;
-  bool want_w = false, tolx = false;
+  bool want_w = false, tolx = false, neals_tol = false;
   int cur = 0;                      // which of W[2] / H[2] holds the factors
   int nact = 0;                     // restarts in pk
   std::vector<char> archived;       // by rid: rows already in Hfin / Wfin
@@ -622,6 +629,8 @@ int check_args(Sweep& s, nmfc_engine* e, const int* ks, int nk, int R, const nmf
   }
   // nmfc_engine_set_euclid: FIXED means fixed, every other value (the default included) the script's membership rule
   if (e->euclid) opts.stop_rule = opts.stop_rule == NMFC_STOP_FIXED ? STOP_FIXED : STOP_MEMBER;
+  // nmfc_engine_set_neals: FIXED means fixed, every other value the TolX / TolFun rule tested on every iteration > 1
+  if (e->neals) opts.stop_rule = opts.stop_rule == NMFC_STOP_FIXED ? STOP_FIXED : STOP_TOLX;
   HIPCHK(hipSetDevice(e->dev));
   return 0;
 }
@@ -667,7 +676,7 @@ int plan_jobs(Sweep& s) {
   }
   // small shapes: one persistent workgroup per 16-column block runs the whole loop (a function of m, n and
   // the stop rule only, so a job takes the same path -- and gives the same bits -- in any batch)
-  s.small = e->small_ok && e->m_pad <= 1024 && n <= 64 && s.opts.stop_rule != NMFC_STOP_TOLX && !e->euclid;
+  s.small = e->small_ok && e->m_pad <= 1024 && n <= 64 && s.opts.stop_rule != NMFC_STOP_TOLX && !e->euclid && !e->neals;
   // ... and there, a restart the solo kernels take (rank 2..8 on gct-sized shapes, nmfc_mu_solo_fits: k_solo_mu for
   // ranks 2..4, k_solo8_mu for 5..8) runs on one workgroup of its own, the others in k_small_mu blocks; the choice is a
   // function of (m, n, k) only, so a job gives the same bits in any batch and on any number of GPUs.  Through the
@@ -685,7 +694,8 @@ int plan_jobs(Sweep& s) {
   s.g_ld = e->n_cols_pad;
   s.g_split = s.cap_cols * s.g_ld;
   s.cls_ld = std::max<long>(n, KMAX);
-  s.tolx = s.opts.stop_rule == NMFC_STOP_TOLX;
+  s.tolx = s.opts.stop_rule == NMFC_STOP_TOLX && !e->neals;   // nmf_neals folds the W maxima into its W solve
+  s.neals_tol = e->neals && s.opts.stop_rule == NMFC_STOP_TOLX;
   s.nact = nj;
   s.archived.assign(nj, 0);
   s.si.assign(nj, 0);
@@ -726,6 +736,14 @@ int ensure_buffers(Sweep& s) {
     return -1;
   if (s.tolx && e->Wsnap.ensure(sizeof(double) * cap_cols * e->m_pad)) return -1;
   hipStream_t st = e->st;
+  if (e->neals) {
+    if (e->Craw.ensure(sizeof(double) * cap_cols * e->m_pad) || e->lupiv.ensure(sizeof(int) * cap_cols) ||
+        e->neals_wd.ensure(sizeof(unsigned long long) * nj) || e->neals_wo.ensure(sizeof(unsigned long long) * nj))
+      return -1;
+    HIPCHK(hipMemsetAsync(e->lupiv.p, 0, sizeof(int) * cap_cols, st));
+    HIPCHK(hipMemsetAsync(e->neals_wd.p, 0, sizeof(unsigned long long) * nj, st));
+    HIPCHK(hipMemsetAsync(e->neals_wo.p, 0, sizeof(unsigned long long) * nj, st));
+  }
   if (upload_packing(e, pk)) return -1;
   HIPCHK(hipMemcpyAsync(e->slot.p, s.rslot.data(), sizeof(int) * nj, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(e->stop_iter.p, 0, sizeof(int) * nj, st));
@@ -1094,6 +1112,7 @@ struct ChunkPlan {
   int ngt_ahtw, grid_ahtw;
   AhtwKernel ka;   // the full-width A h^T tile
   AhtwKernelE kae; // ... with the Euclidean NMF() W rule (nmfc_engine_set_euclid)
+  AhtwKernelE kan; // ... storing the raw product for nmf_neals' W solve (nmfc_engine_set_neals; the same signature)
 };
 
 int launch_wta(Sweep& s, const ChunkPlan& cp, int* gsplit) {
@@ -1109,6 +1128,14 @@ int launch_wta(Sweep& s, const ChunkPlan& cp, int* gsplit) {
 
 void launch_hupdate(const Sweep& s, int iter, int gsplit) {
   nmfc_engine* e = s.e;
+  if (e->neals) {   // nmf_neals: the H solve, H H^T and its LU (nmfc_engine_set_neals)
+    hipLaunchKernelGGL(k_hupdate_neals, dim3(s.nact), dim3(NTH), 0, e->st, iter, s.opts.maxiter, (int)s.neals_tol,
+                       e->rinfo.as<RestartInfo>(), e->n, e->n_pad, e->Gpart.as<double>(), s.g_ld, s.g_split, gsplit,
+                       e->nsplit, e->SWpart.as<double>(), s.sw_total, e->H[s.cur].as<double>(), e->SH.as<double>(),
+                       e->stop_iter.as<int>(), e->stop_reason.as<int>(), e->n_stopped.as<int>(), e->SHP.as<double>(),
+                       e->lupiv.as<int>(), e->colact.as<int>(), e->Hstat.as<double>());
+    return;
+  }
   if (e->euclid) {   // the Euclidean NMF() rule and its membership check (nmfc_engine_set_euclid)
     const StopMember stop{s.opts.stop_rule, e->euc_stopconv, e->euc_stopfreq};
     hipLaunchKernelGGL((k_hupdate<32, 4, RULE_EUCLID>), dim3(s.nact), dim3(NTH), 0, e->st, iter, s.opts.maxiter, stop,
@@ -1130,6 +1157,28 @@ void launch_hupdate(const Sweep& s, int iter, int gsplit) {
 void launch_ahtw(const Sweep& s, const ChunkPlan& cp, int iter) {
   nmfc_engine* e = s.e;
   ++(cp.nblk > 0 ? e->info.ahtw_narrow : cp.tc.ahtw_small ? e->info.ahtw_64 : e->info.ahtw_128);
+  if (e->neals) {   // the same grids; H A^T goes to Craw, then the W solve and, under the TolX rule, the stop test
+    if (cp.nblk > 0)
+      hipLaunchKernelGGL((k_ahtw4<GT / 4, GT_NBUF, 1, 16, 2, false, false, RULE_NEALS>), dim3(4 * e->ngt * cp.nblk),
+                         dim3(128), 0, e->st, iter, e->H[s.cur].as<double>(), e->n_pad, e->Arm.as<double>(), e->m_pad,
+                         e->Craw.as<double>(), e->SHP.as<double>(), e->colinfo.as<ColInfo>(), e->colact.as<int>(),
+                         cp.nblk, GeneTiles{4 * e->ngt, e->m});
+    else
+      hipLaunchKernelGGL(cp.kan, dim3(cp.grid_ahtw), dim3(256), 0, e->st, iter, e->H[s.cur].as<double>(), e->n_pad,
+                         e->Arm.as<double>(), e->m_pad, e->Craw.as<double>(), e->SHP.as<double>(),
+                         e->colinfo.as<ColInfo>(), e->colact.as<int>(), cp.lp, GeneTiles{cp.ngt_ahtw, e->m});
+    const int check = s.neals_tol && iter > 1;
+    hipLaunchKernelGGL(k_wsolve_neals, dim3(s.nact, (unsigned)((e->m_pad + NT - 1) / NT)), dim3(NT), 0, e->st, iter, check,
+                       e->rinfo.as<RestartInfo>(), e->m, e->m_pad, e->Craw.as<double>(), e->W[s.cur].as<double>(),
+                       e->SHP.as<double>(), e->lupiv.as<int>(), e->colact.as<int>(),
+                       e->neals_wd.as<unsigned long long>(), e->neals_wo.as<unsigned long long>());
+    if (check)
+      hipLaunchKernelGGL(k_neals_stop, dim3((s.nact + NT - 1) / NT), dim3(NT), 0, e->st, iter, s.nact,
+                         e->rinfo.as<RestartInfo>(), e->colact.as<int>(), e->Hstat.as<double>(),
+                         e->neals_wd.as<unsigned long long>(), e->neals_wo.as<unsigned long long>(), s.opts.TolX,
+                         s.opts.TolFun, e->stop_iter.as<int>(), e->stop_reason.as<int>(), e->n_stopped.as<int>());
+    return;
+  }
   if (e->euclid) {   // the same grids, the Euclidean NMF() W rule; the kernels also take m (padded gene rows stay +0.0)
     if (cp.nblk > 0)
       hipLaunchKernelGGL((k_ahtw4<GT / 4, GT_NBUF, 1, 16, 2, false, false, RULE_EUCLID>), dim3(4 * e->ngt * cp.nblk),
@@ -1173,6 +1222,11 @@ ChunkPlan plan_chunk(const Sweep& s) {
                                   : k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, false, RE>)
                             : (kh ? k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2, RE>
                                   : k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, false, RE>);
+  constexpr int RN = RULE_NEALS;
+  cp.kan = cp.tc.ahtw_small ? (kh ? k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2, RN>
+                                  : k_ahtw4<GT / 2, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, false, RN>)
+                            : (kh ? k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, AHTW_NBUF == 2, RN>
+                                  : k_ahtw4<GT, AHTW_NBUF, 1, PANEL, 4, AHTW_LATE, false, RN>);
   return cp;
 }
 
@@ -1440,6 +1494,9 @@ void account_kernels(Sweep& s, nmfc_result* out) {
     // A h^T + W update: h, W0 read, W written
     ba_ahtw += itr * 8.0 * k * (2.0 * m + n);
     b_ahtw += itr * 8.0 * k * (2.0 * m + n + KMAX);
+    // nmf_neals: the W side also writes H A^T to Craw and reads it back in k_wsolve_neals (design bytes only; the
+    // flops stay: the two substitutions cost the 2 m k^2 that E = W0 (h h^T) costs)
+    if (e->neals) b_ahtw += itr * 16.0 * k * m;
     // H update (SURVEY 8(d) B_ew, H side): H, numerator, denominator read, H written = 32 n k
     ba_hupd += itr * 32.0 * n * k;
     b_hupd += itr * 8.0 * (k * n * (ns + 2.0) + k * k * (ns + 2.0) + k * KMAX);
@@ -1660,12 +1717,43 @@ int nmfc_engine_set_euclid(nmfc_engine* e, int enable, int stopconv, int stopfre
     errorf("nmfc_engine_set_euclid: stopconv = %d and stopfreq = %d must both be >= 1", stopconv, stopfreq);
     return -1;
   }
+  if (enable && e->neals) {
+    errorf("nmfc_engine_set_euclid: the NEALS rule is enabled on this engine (nmfc_engine_set_neals(e, 0) first)");
+    return -1;
+  }
   e->euclid = enable != 0;
   if (enable) {
     e->euc_stopconv = stopconv;
     e->euc_stopfreq = stopfreq;
   }
   return 0;
+}
+
+int nmfc_engine_set_neals(nmfc_engine* e, int enable) {
+  if (!e) {
+    errorf("nmfc_engine_set_neals: no engine");
+    return -1;
+  }
+  if (enable && e->euclid) {
+    errorf("nmfc_engine_set_neals: the Euclidean NMF() rule is enabled on this engine (nmfc_engine_set_euclid(e, 0, ..) first)");
+    return -1;
+  }
+  e->neals = enable != 0;
+  return 0;
+}
+
+int nmfc_engine_neals_status(nmfc_engine* e, int32_t* status_out) {
+  if (!e) {
+    errorf("nmfc_engine_neals_status: no engine");
+    return -1;
+  }
+  if (!e->neals_valid) {
+    errorf("nmfc_engine_neals_status: the last run on this engine was not a NEALS run or failed (nmfc_engine_set_neals)");
+    return -1;
+  }
+  if (status_out)
+    for (size_t j = 0; j < e->neals_status.size(); ++j) status_out[j] = e->neals_status[j];
+  return (int)e->neals_status.size();
 }
 
 namespace {
@@ -1770,6 +1858,7 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
   using clk = std::chrono::steady_clock;
   Sweep s;
   if (e) e->resid_valid = false;   // until this run has filled them
+  if (e) e->neals_valid = false;
   if (check_args(s, e, ks, nk, R, opts_in)) return -1;
   const auto t_start = clk::now();
   for (int x = 0; x < KID_N; ++x) {
@@ -1801,6 +1890,12 @@ int nmfc_engine_run(nmfc_engine* e, const int* ks, int nk, int R, const nmfc_swe
   if (archive_rest(s) || residual_pass(s) || labels_counts_consensus(s, out)) return -1;
   account_kernels(s, out);
   if (download_factors(s, out)) return -1;
+  if (e->neals) {   // what nmfc_engine_neals_status reads of this run
+    e->neals_status.assign(s.nj, 0);
+    for (int rid = 0; rid < s.nj; ++rid)
+      e->neals_status[s.rslot[rid]] = s.sr[rid] == NEALS_ZERO_G ? 1 : s.sr[rid] == NEALS_ZERO_S ? 2 : 0;
+    e->neals_valid = true;
+  }
   if (e->residuals) {   // what nmfc_engine_residuals / nmfc_engine_best read of this run
     e->last_ks.assign(ks, ks + nk);
     e->last_jb = s.jb;

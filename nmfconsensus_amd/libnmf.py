@@ -35,6 +35,25 @@ def nmf_mu(a, w0, h0, maxiter: int, TolX: float = 1e-4, TolFun: float = 1e-4):
             "pTolFun": TolFun, "ret": ret}
 
 
+def nmf_neals(a, w0, h0, maxiter: int, TolX: float = 1e-4, TolFun: float = 1e-4):
+    """.C('nmf_neals', ...) on copies of the arguments: returns (W, H, iterations, dnorm).  iterations is *maxiter on
+    return (the stopping iteration, or the cap), dnorm the return value: calculateNorm of the final factors, or -1 after
+    an error (a rank outside 2..16, or an exactly zero pivot: include/libnmf_compat.h).  h0 gives the shape only: it is
+    not an input of nmf_neals."""
+    a, w0, h0 = _f(a), _f(w0), _f(h0)
+    m, n = a.shape
+    k = w0.shape[1]
+    if w0.shape != (m, k) or h0.shape != (k, n):
+        raise ValueError("shape mismatch between a, w0 and h0")
+    c = ctypes.c_int
+    mi = c(int(maxiter))
+    tx, tf = ctypes.c_double(TolX), ctypes.c_double(TolFun)
+    ret = _lib.lib().nmf_neals(a.ctypes.data_as(_dp), w0.ctypes.data_as(_dp), h0.ctypes.data_as(_dp),
+                               ctypes.byref(c(m)), ctypes.byref(c(n)), ctypes.byref(c(k)), ctypes.byref(mi),
+                               ctypes.byref(tx), ctypes.byref(tf))
+    return w0, h0, mi.value, ret
+
+
 def set_default_opts() -> _lib.OptionsT:
     o = _lib.OptionsT()
     _lib.lib().set_default_opts(ctypes.byref(o))

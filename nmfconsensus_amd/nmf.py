@@ -91,6 +91,8 @@ class SweepResult:
     # brunet.nmfconsensus(error_function="euclidean"): NMF()'s error.v of the final factors, sqrt(sum((V - W H)^2)) / (m n)
     error: np.ndarray | None = None            # (nk, R) float64
     best_error: list | None = None             # per k: the smallest (best_restart: its restart, the lowest on ties)
+    # Engine.run(neals=True): per job 0, 1 (exactly zero pivot in the H solve) or 2 (in the W solve); None for other runs
+    neals_status: np.ndarray | None = None     # (njobs,) int32
 
 
 class Engine:
@@ -117,6 +119,7 @@ class Engine:
         self.device = self.L.nmfc_engine_device(h)   # HIP ordinal resolved at creation (device -1: the current one)
         self._residuals = False
         self._euclid = None
+        self._neals = False
 
     def close(self):
         if getattr(self, "h", None):
@@ -152,6 +155,23 @@ class Engine:
         if self.L.nmfc_engine_set_euclid(self.h, 1 if on else 0, int(stopconv), int(stopfreq)) != 0:
             raise ValueError(f"nmfc_engine_set_euclid failed: {_lib.last_error()}")
         self._euclid = dict(stopconv=int(stopconv), stopfreq=int(stopfreq)) if on else None
+
+    def set_neals(self, on: bool):
+        """Later run() calls use libnmf's nmf_neals update (normal-equation ALS: two k x k LU solves per iteration, clamped
+        at zero) and its stop rule: stop_rule=STOP_FIXED means exactly maxiter iterations, every other value the TolX /
+        TolFun test on every iteration > 1 (nmfc_engine_set_neals).  Fails while the Euclidean rule is on.  on=False
+        restores the nmf_mu runs."""
+        if self.L.nmfc_engine_set_neals(self.h, 1 if on else 0) != 0:
+            raise ValueError(f"nmfc_engine_set_neals failed: {_lib.last_error()}")
+        self._neals = bool(on)
+
+    def neals_status(self) -> np.ndarray:
+        """Per shard job of the last run, which must have been a NEALS run: 0, 1 or 2 (nmfc_engine_neals_status)."""
+        out = np.zeros(max(1, self._last_nj), dtype=np.int32)
+        got = self.L.nmfc_engine_neals_status(self.h, out.ctypes.data_as(_ip))
+        if got < 0:
+            raise RuntimeError(f"nmfc_engine_neals_status failed: {_lib.last_error()}")
+        return out[:got]
 
     def residuals(self) -> np.ndarray:
         """dnorm of every shard job of the last run, which must have had residuals enabled (nmfc_engine_residuals)."""
@@ -225,7 +245,8 @@ class Engine:
             want_factors: bool = False, want_counts: bool = True, counts_device_ptr: int | None = None,
             check_every: int = 4, min_init: int = 0, max_init: int = 1, verbose: bool = False,
             TolX: float = 1e-4, TolFun: float = 1e-4, init_stream: int = INIT_LIBNMF, want_h: bool = False,
-            want_residuals: bool = False, want_best: bool = False, euclid: dict | None = None) -> SweepResult:
+            want_residuals: bool = False, want_best: bool = False, euclid: dict | None = None,
+            neals: bool | None = None) -> SweepResult:
         """One sweep of the (k, restart) job grid (or its shard [job_begin, job_end)).  want_factors: final W and
         H of every job; want_h: final H only (the C3-sized checks: W of 1800 jobs is 1.7 GB of host memory).
         want_residuals: SweepResult.dnorm, every job's ||A - W H||_F / sqrt(m n), from one batched pass on the device
@@ -233,7 +254,15 @@ class Engine:
         with the smallest dnorm and its W, H -- the only factors that leave the device.  Both are enabled for this
         call only; the engine's set_residuals() setting (which, when on, fills dnorm on every run) is restored
         afterwards.  euclid=dict(stopconv=, stopfreq=): this call runs the BROAD script's Euclidean NMF() (set_euclid)
-        and the engine's set_euclid() setting is restored afterwards; None leaves that setting as it is."""
+        and the engine's set_euclid() setting is restored afterwards; None leaves that setting as it is.
+        neals=True / False: this call runs with the nmf_neals rule on / off (set_neals) and the engine's setting is
+        restored afterwards; None leaves it as it is.  Under that rule H_init may be omitted (H0 is not an input of
+        nmf_neals), and SweepResult.neals_status is filled.  neals=True together with euclid=, or with the engine's
+        Euclidean rule on, raises before any setting has changed."""
+        neals_on = self._neals if neals is None else bool(neals)
+        if neals_on and (euclid is not None or self._euclid is not None):
+            raise ValueError("the NEALS and the Euclidean NMF() rules exclude each other: turn one off "
+                             "(neals=False, or set_euclid(False))")
         ks = [int(k) for k in ks]
         nk = len(ks)
         njobs_all = nk * R
@@ -275,6 +304,8 @@ class Engine:
             hflat = np.zeros(sum(k * n for k in jk), dtype=np.float64)
             res.H = hflat.ctypes.data_as(_dp)
         wi = hi = None
+        if neals_on and W_init is not None and H_init is None:
+            H_init = [np.zeros((w.shape[1], n)) for w in map(_f64, W_init)]
         if W_init is not None or H_init is not None:
             if W_init is None or H_init is None:
                 raise ValueError("W_init and H_init must be given together")
@@ -283,9 +314,18 @@ class Engine:
             if wi.size != sum(m * k for k in jk) or hi.size != sum(k * n for k in jk):
                 raise ValueError("W_init/H_init sizes do not match the job shard")
         ks_arr = np.array(ks, dtype=np.int32)
-        prev_euclid = self._euclid
+        prev_euclid, prev_neals = self._euclid, self._neals
+        if neals is not None and not neals_on and prev_neals:
+            self.set_neals(False)
         if euclid is not None:   # first: bad arguments raise before any other setting has changed
-            self.set_euclid(True, **euclid)
+            try:
+                self.set_euclid(True, **euclid)
+            except ValueError:
+                if self._neals != prev_neals:
+                    self.set_neals(prev_neals)
+                raise
+        if neals_on and not prev_neals:
+            self.set_neals(True)
         prev = self._residuals
         want_residuals = want_residuals or want_best or prev
         if want_residuals != prev:
@@ -297,13 +337,18 @@ class Engine:
         finally:
             if want_residuals != prev:
                 self.set_residuals(prev)
+            if self._neals and not prev_neals:
+                self.set_neals(False)
             if euclid is not None:
                 self.set_euclid(prev_euclid is not None, **(prev_euclid or {}))
+            if prev_neals and not self._neals:
+                self.set_neals(True)
         if rc != 0:
             raise RuntimeError(f"nmfc_engine_run failed: {_lib.last_error()}")
         self._last_ks, self._last_nj = ks, nj
         dnorm = self.residuals() if want_residuals else None
         best = self.best() if want_best else None
+        status = self.neals_status() if neals_on else None
         Ws = Hs = None
         if want_factors or want_h:
             Ws = [] if want_factors else None
@@ -318,7 +363,8 @@ class Engine:
         return SweepResult(ks=ks, R=R, n=n, counts=counts, consensus=consensus, labels=labels, iters=iters,
                            stopped_early=early, W=Ws, H=Hs, seconds_total=res.seconds_total,
                            seconds_iterate=res.seconds_iterate, restart_iterations=res.restart_iterations,
-                           max_iter_run=res.max_iter_run, job_begin=jb, job_end=je, dnorm=dnorm, best=best)
+                           max_iter_run=res.max_iter_run, job_begin=jb, job_end=je, dnorm=dnorm, best=best,
+                           neals_status=status)
 
 
 _DONMF = {"A": None, "eng": None, "device": None}
@@ -357,13 +403,25 @@ def release_doNMF_engine():
 
 
 def doNMF(A, k: int, maxniter: int, seed: int = 123, tolerance: float = 1e-4, num_clusterings=None,
-          *, job_id: int = 1, stop_rule: int = STOP_REF_COMPAT, init_stream: int = INIT_LIBNMF, device: int = -1):
+          *, job_id: int = 1, stop_rule: int = STOP_REF_COMPAT, init_stream: int = INIT_LIBNMF, device: int = -1,
+          algorithm: str = "mu"):
     """nmf.r:23-51 -- one restart: init W, H (generateMatrix(ran) stream, seed + job_id - 1), run the
     MU loop on the GPU, return dict(W=m x k, H=k x n, iter=iterations).  `tolerance` is accepted and
     unused, like the reference (nmf_mu.c:92-93).  The engine (A resident in HBM in its layouts) is kept for
-    the next call with the same A (release_doNMF_engine() frees it)."""
-    del tolerance, num_clusterings
+    the next call with the same A (release_doNMF_engine() frees it).
+    algorithm="neals": libnmf's nmf_neals instead of nmf_mu (Engine.set_neals); `tolerance` is its TolX (TolFun keeps
+    1e-4), stop_rule=STOP_FIXED still means exactly maxniter iterations, and the dict also holds 'status' (0, or 1 / 2
+    for an exactly zero pivot in the H / W solve)."""
+    if algorithm not in ("mu", "neals"):
+        raise ValueError(f"algorithm must be 'mu' or 'neals', not {algorithm!r}")
+    del num_clusterings
     A = _f64(A)
+    if algorithm == "neals":
+        with _DONMF_LOCK:
+            eng = _donmf_engine(A, device)
+            r = eng.run([k], 1, maxiter=maxniter, seed=seed + job_id - 1, stop_rule=stop_rule, want_factors=True,
+                        want_counts=False, init_stream=init_stream, TolX=tolerance, neals=True)
+        return {"W": r.W[0], "H": r.H[0], "iter": int(r.iters[0]), "status": int(r.neals_status[0])}
     with _DONMF_LOCK:
         eng = _donmf_engine(A, device)
         # a single-job "grid" whose job seed is seed + job_id - 1
@@ -394,22 +452,28 @@ def createJobArray(A, k, num_clusterings: int, maxniter: int, seed: int, toleran
 
 def runNMFinJobs(A, k, num_clusterings: int, maxniter: int, seed: int, njobs: int = 1, *,
                  stop_rule: int = STOP_REF_COMPAT, label_rule: int = LABEL_ARGMAX, save_dir: str | None = None,
-                 device: int = -1, init_stream: int = INIT_LIBNMF, want_best: bool = False):
+                 device: int = -1, init_stream: int = INIT_LIBNMF, want_best: bool = False, algorithm: str = "mu",
+                 tolerance: float = 1e-4):
     """nmf.r:106-119: run every (k, restart) job, reduce per k to a consensus matrix, then cophenetic,
     ordering and membership (computeConsensusAndSaveFiles).  `njobs` (BatchJobs chunks) has no effect:
     all jobs run as one batched sweep on the GPU (use nmfconsensus_amd.distributed for several GPUs).
     Returns the dict produced by computeConsensusAndSaveFiles, plus the raw SweepResult under 'sweep'.
     want_best: also 'best', {k: dict(job, dnorm, W, H)}: per rank the restart with the smallest residual norm and its
     metagenes (the restart nmf.r:200-203's commented-out "Example H matrix" plots would show), and 'dnorm', every job's
-    residual norm in job order."""
+    residual norm in job order.
+    algorithm="neals": every job runs libnmf's nmf_neals (Engine.set_neals) with TolX = `tolerance`; "mu" (the default)
+    ignores `tolerance`, like the reference."""
     del njobs
+    if algorithm not in ("mu", "neals"):
+        raise ValueError(f"algorithm must be 'mu' or 'neals', not {algorithm!r}")
     ks = list(k)
     if 1 in ks:
         raise ValueError("Need at least two clusters to compute standard deviation")   # nmf.r:107-108
     reg = createJobArray(A, ks, num_clusterings, maxniter, seed)
     with Engine(reg.A, device) as eng:
         sw = eng.run(ks, num_clusterings, maxiter=maxniter, seed=seed, stop_rule=stop_rule, label_rule=label_rule,
-                     init_stream=init_stream, want_best=want_best)
+                     init_stream=init_stream, want_best=want_best,
+                     **(dict(neals=True, TolX=tolerance) if algorithm == "neals" else {}))
     result = {str(kk): sw.consensus[i] for i, kk in enumerate(ks)}
     out = computeConsensusAndSaveFiles(result, save_dir=save_dir)
     out["sweep"] = sw
