@@ -6,6 +6,7 @@ The library is the product: HIP kernels + the C ABI of include/libnmf_compat.h a
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 
@@ -14,16 +15,26 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libnmf.so")
 SOURCES = ["engine.hip", "compat.hip", "brunet.hip", "generic.hip", "solo.hip", "hclust.cpp"]
-HEADERS = ["nmfc_kernels.hpp", "nmfc_tuning.hpp", "nmfc_internal.hpp", "nmfc_host.hpp", "lane_pool.hpp", "rmt.hpp", "../../include/nmfc.h", "../../include/libnmf_compat.h"]
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + ["../../include/nmfc.h", "../../include/libnmf_compat.h"]
 ARCH = os.environ.get("NMFC_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def kernel_headers() -> list[str]:
+    """nmfc_kernels.hpp (the umbrella) and the kernel-family headers it includes, in its order; each is one of HEADERS.
+    Only the umbrella's own #include lines are read: a family header includes family headers the umbrella also names,
+    and beside them only nmfc_tuning.hpp and rmt.hpp (source_sha256 adds the first; the second holds no engine kernel)."""
+    with open(os.path.join(CSRC, "nmfc_kernels.hpp")) as fh:
+        incs = re.findall(r'^#include "(\w+\.hpp)"', fh.read(), re.M)
+    assert incs and set(incs) <= set(HEADERS), incs
+    return ["nmfc_kernels.hpp", *incs]
 
 
 def source_sha256() -> str:
     """Hash of the engine's kernel + host sources: tags PMC profiles with the code they measured."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("nmfc_kernels.hpp", "engine.hip", "nmfc_tuning.hpp"):
+    for f in (*kernel_headers(), "engine.hip", "nmfc_tuning.hpp"):
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()

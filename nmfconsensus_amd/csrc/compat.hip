@@ -18,7 +18,8 @@
 #include "../../include/nmfc.h"
 #include "nmfc_host.hpp"
 #include "nmfc_internal.hpp"
-#include "nmfc_kernels.hpp"
+#include "nmfc_common.hpp"
+#include "nmfc_norm.hpp"
 
 namespace {
 constexpr size_t NORM_BLOCKS = 4096;   // grid of the norm / max-change partial passes (>> 256 CUs)

@@ -19,7 +19,7 @@
 #include "../../include/nmfc.h"
 #include "nmfc_host.hpp"
 #include "nmfc_internal.hpp"
-#include "nmfc_kernels.hpp"
+#include "nmfc_common.hpp"
 
 namespace {
 

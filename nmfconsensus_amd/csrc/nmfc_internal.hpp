@@ -7,7 +7,7 @@
 #include "../../include/nmfc.h"
 
 namespace nmfc {
-struct SoloJob;   // nmfc_kernels.hpp
+struct SoloJob;   // nmfc_common.hpp (brunet.hip and the host-runtime driver include this file without it)
 }
 
 // Exported but in no public header: compat.hip is also built on its own and linked against the library (the host

@@ -88,7 +88,7 @@ KL_EPS = 2.220446049250313e-16      # .Machine$double.eps, brunet.hip EPS
 # global scale of A per update rule (conditions of test_widerange_reference.py: MU puts the W-side denominators on
 # both sides of 1e-9; KL keeps A <= 2^64 and sum(A) <= 2^100)
 ALPHA = {"mu": 10.0 ** -9.5, "kl": 1.0, "euclid": 1e-26}
-EUCLID_EPS = 2.0 ** -52             # .Machine$double.eps, nmfc_kernels.hpp R_EPS: the constant the Euclidean rule adds
+EUCLID_EPS = 2.0 ** -52             # .Machine$double.eps, nmfc_common.hpp R_EPS: the constant the Euclidean rule adds
 # Euclid: with A at 1e-26 and W0 at 2^-34 the products H0 * q and (W0 * num) / den of the first update lie on both
 # sides of 2^-52 for every shape of EUCLID_BATCHES
 EUCLID_W0_SCALE = 2.0 ** -34
